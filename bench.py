@@ -5,7 +5,7 @@ One "step" = one SNP-minibatch update = tsamd_snp_update semantics
 (optimize_lambda(loc), src/snpsamplinge.cc:320-366, plus the gamma/Elogtheta
 step of that SNP, :695-740), on synthetic PSD genotypes resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -79,6 +79,8 @@ def parse():
                     help="validation locations of the validation-block leg (-1: the reference's sample size, floor(0.005 L), at most 5000; 0: skip)")
     ap.add_argument("--ramp-seconds", type=float, default=0.3,
                     help="untimed priming schedule queued right ahead of the warm-up (set-up; 0 = none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (a seeded sample; see dump_outputs) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -104,6 +106,41 @@ def gather_bytes(local, dist, rank):
     out = [None] * dist.get_world_size() if rank == 0 else None
     dist.gather_object(local, out, dst=0)
     return out
+
+
+DUMP_ROWS = 1 << 16   # individuals whose gamma / E[log theta] --dump-outputs writes (a fixed, seeded sample)
+DUMP_LOCS = 1 << 12   # timed locations whose lambda --dump-outputs writes (likewise)
+
+
+def dump_outputs(out_dir, eng, dist, rank, world, n, k, sb, sc, seed, timed_locs):
+    """--dump-outputs: what the timed schedule left for a caller of run_schedule to read back, taken after its last step and
+    before any later leg updates the engine again -- lambda of the last step's location, lambda of a sample of the timed
+    locations, gamma and E[log theta] of a sample of the individuals (gathered over the ranks' shards), float64.  The
+    samples are drawn from --seed, so two builds run with the same arguments write files that compare entry by entry: bit
+    for bit on one GPU; with N > 1 ranks to rounding only, because choose_exchange picks the exchange and launch mode by
+    timing, and those agree to rounding, not bit for bit."""
+    size = min(n, DUMP_ROWS, (48 << 20) // (2 * 8 * k))     # (gamma and E[log theta] within 48 MB of the 64 MB at any K)
+    rows = np.sort(np.random.default_rng(seed + 6).choice(n, size=size, replace=False))
+    mine = rows[(rows >= sb) & (rows < sb + sc)] - sb
+    local = (eng.get_gamma()[mine], eng.get_elogtheta()[mine])
+    if dist is not None:
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(local, parts, dst=0)
+        if rank == 0:
+            local = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+    if rank != 0:
+        return
+    uniq = np.unique(timed_locs)
+    locs = np.sort(np.random.default_rng(seed + 7).choice(uniq, size=min(uniq.size, DUMP_LOCS), replace=False))
+    last = int(timed_locs[-1])
+    arrays = {
+        "gamma": local[0], "elogtheta": local[1], "gamma_rows": rows.astype(np.float64),
+        "lambda_last": eng.get_lambda(last, 1)[0],
+        "lambda": np.stack([eng.get_lambda(int(j), 1)[0] for j in locs]), "lambda_locs": locs.astype(np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def choose_exchange(ts, dist, rank, world, local_rank, n, k, theta_shard, gamma_full, shard, cores):
@@ -925,21 +962,18 @@ def main():
     # contract's `--steps 20 --warmup 5` would lie entirely inside that transient.  So about --ramp-seconds of the same
     # updates are queued right AHEAD of the warm-up, with no synchronisation in between: the device is at its steady
     # clocks when the warm-up ends, and the one barrier + synchronise that the contract puts before the timed region is
-    # kept as short as possible (the counters read there come from pinned memory, no copy).  Sized from a short pilot.
+    # kept as short as possible (the counters read there come from pinned memory, no copy).  Sized from the shape, not from a
+    # timed pilot: the timed updates must start from the same state in every run with the same arguments (--dump-outputs), so
+    # the number of updates ahead of them may not depend on a clock.  Per update ~0.8e-11 s x N x K per rank + 2 us, on the
+    # long side (one MI355X: 0.076 ms at N = 1M, K = 8; 0.28 ms at K = 20), the same on every rank.  Ranks that share one
+    # device (TSAMD_BENCH_DEVICE) time-slice it, so there the ramp runs about world times longer than --ramp-seconds (untimed).  A short fixed schedule
+    # and a synchronisation go first, so that first-launch costs are paid before the ramp is queued.
     ramp_n = 0
     if args.ramp_seconds > 0:
-        pilot = np.random.default_rng(args.seed + 4).integers(0, l, size=64).astype(np.uint32)
-        eng.run_schedule(pilot[:8])
+        eng.run_schedule(np.random.default_rng(args.seed + 4).integers(0, l, size=64).astype(np.uint32))
         eng.synchronize()
-        tp = time.perf_counter()
-        eng.run_schedule(pilot[8:])
-        eng.synchronize()
-        per_update = (time.perf_counter() - tp) / 56.0
-        if dist is not None:   # every rank must queue the same number of updates
-            tpu = torch.tensor([per_update], dtype=torch.float64)
-            dist.all_reduce(tpu, op=dist.ReduceOp.MAX)
-            per_update = float(tpu.item())
-        ramp_n = int(min(20000, max(100, args.ramp_seconds / max(per_update, 1e-6))))
+        per_update = 2e-6 + 0.8e-11 * n * k / world
+        ramp_n = int(min(20000, max(100, args.ramp_seconds / per_update)))
     setup_s = time.time() - t_setup
 
     locs = np.random.default_rng(args.seed + 3).integers(0, l, size=args.warmup + args.steps).astype(np.uint32)
@@ -979,6 +1013,13 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+
+    if args.dump_outputs:
+        try:
+            dump_outputs(args.dump_outputs, eng, dist, rank, world, n, k, sb, sc, args.seed, locs[args.warmup:])
+        except Exception as exc:  # noqa: BLE001
+            err = exc
+        fail_together(err is None, dist, f"--dump-outputs: {err}")
 
     value = args.steps / dt
     mean_passes = passes / max(1, args.steps)

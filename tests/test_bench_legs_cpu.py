@@ -60,6 +60,9 @@ class _FakeEngine:
     def get_counts(self):
         return self.sh.orc.c_indiv()[self.sh.b:self.sh.b + self.sh.c]
 
+    def get_elogtheta(self):
+        return self.sh.orc.elogtheta()[self.sh.b:self.sh.b + self.sh.c]
+
     def download_bed(self, j):
         b, c = self.sh.b, self.sh.c
         return self.payload[j, b // 4:(b + c + 3) // 4]
@@ -174,3 +177,77 @@ def test_one_failing_leg_costs_only_itself(tmp_path, fail_leg, fail_rank):
         assert legs["parity_vs_cpu_baseline"].startswith("skipped") and legs["validation_block"].startswith("skipped")
     if fail_leg == "stream_probe":
         assert m["roofline"]["probe_read_us"] is None
+
+
+def _dump_worker(rank, world, port, out_dir, sample=None):
+    import datetime
+    import sys
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    import terastructure_amd as real
+
+    if sample is not None:                      # (rows, locations): samples smaller than the run, as at the benchmark's size
+        bench.DUMP_ROWS, bench.DUMP_LOCS = sample
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+    n, l, k = 1003, 24, 5
+    ts = types.SimpleNamespace(shard_range=real.shard_range)
+    eng = _FakeEngine(ts, n, l, k, rank, world, None, 0)
+    locs = np.random.default_rng(1).integers(0, l, size=14).astype(np.uint32)
+    eng.run_schedule(locs)
+    bench.dump_outputs(out_dir, eng, dist, rank, world, n, k, eng.shard_begin, eng.shard_count, 3, locs[2:])
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _dump_and_oracle(tmp_path, sample=None):
+    """(the files --dump-outputs wrote on 2 ranks, the timed locations, one unsharded oracle after the same updates)"""
+    import oracle_py as op
+
+    world, n, l, k = 2, 1003, 24, 5
+    mp.spawn(_dump_worker, args=(world, _free_port(), str(tmp_path), sample), nprocs=world, join=True)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(got) == {"gamma", "elogtheta", "gamma_rows", "lambda_last", "lambda", "lambda_locs"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    locs = np.random.default_rng(1).integers(0, l, size=14).astype(np.uint32)
+    y, _, _ = psd_genotypes(n, l, k, 11, 0.02)
+    orc = op.Oracle(n, l, k)
+    orc.load_bed_payload(pack_bed(y))
+    orc.set_gamma(init_gamma(n, k, 5))
+    for loc in locs:
+        orc.snp_update(int(loc))
+    assert np.allclose(got["gamma"], orc.gamma()[got["gamma_rows"].astype(np.int64)], rtol=1e-12, atol=0)
+    assert np.allclose(got["elogtheta"], orc.elogtheta()[got["gamma_rows"].astype(np.int64)], rtol=1e-12, atol=0)
+    assert np.allclose(got["lambda"], orc.lambda_()[got["lambda_locs"].astype(np.int64)], rtol=1e-12, atol=0)
+    assert np.allclose(got["lambda_last"], orc.lambda_()[locs[-1]], rtol=1e-12, atol=0)
+    return got, locs, orc
+
+
+def test_dump_outputs_is_the_state_of_the_timed_updates(tmp_path):
+    """--dump-outputs: the gathered sample of both shards' gamma / E[log theta] and lambda of the timed locations is what one
+    unsharded oracle holds after the same updates; every file is float64 and the samples are the same from run to run."""
+    got, locs, _ = _dump_and_oracle(tmp_path)
+    assert np.array_equal(got["gamma_rows"], np.arange(1003))             # (n below the sample size: every individual)
+    assert np.array_equal(got["lambda_locs"], np.unique(locs[2:]))        # (fewer than the sample size: all timed locations)
+    again = tmp_path / "again"
+    mp.spawn(_dump_worker, args=(2, _free_port(), str(again)), nprocs=2, join=True)
+    for name, a in got.items():
+        assert np.array_equal(np.load(again / f"{name}.npy"), a), name
+
+
+def test_dump_outputs_samples_across_the_shards(tmp_path):
+    """The sampling branch (N and the timed locations above the sample sizes, as at the benchmark's size): 64 of 1003
+    individuals drawn from --seed, each rank contributing the drawn rows of its own shard, in global order; 5 of the timed
+    locations; the values still the unsharded oracle's."""
+    got, locs, _ = _dump_and_oracle(tmp_path, sample=(64, 5))
+    rows = got["gamma_rows"].astype(np.int64)
+    assert np.array_equal(rows, np.sort(np.random.default_rng(3 + 6).choice(1003, size=64, replace=False)))
+    import terastructure_amd as real
+
+    cut = real.shard_range(1003, 1, 2)[0]
+    assert np.unique(rows).size == 64 and (rows < cut).any() and (rows >= cut).any()     # (rows of both shards)
+    assert got["gamma"].shape == got["elogtheta"].shape == (64, 5)
+    sel = got["lambda_locs"].astype(np.int64)
+    assert sel.size == 5 and np.unique(sel).size == 5 and np.isin(sel, locs[2:]).all()
+    assert got["lambda"].shape == (5, 5, 2)
