@@ -364,6 +364,10 @@ void orc_set_lambda(orc_state *s, uint32_t loc, const double *lam) {
   orc_estimate_beta(s, loc);
 }
 
+void orc_set_counts(orc_state *s, const uint32_t *c) {
+  memcpy(s->c_indiv, c, (size_t)s->c.n * sizeof(uint32_t));
+}
+
 uint32_t orc_set_validation_sample(orc_state *s, orc_rng *r) {
   uint32_t n = s->c.n, l = s->c.l;
   uint32_t per_loc_h = n < 2000 ? (n / 10) : (n / 100);

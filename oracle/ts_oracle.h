@@ -108,6 +108,9 @@ void orc_set_gamma(orc_state *s, const double *gamma);
 /* init_lambda src/snpsamplinge.cc:239-250 */
 void orc_init_lambda(orc_state *s);
 void orc_set_lambda(orc_state *s, uint32_t loc, const double *lam /* [k][2] */);
+/* set the per-individual update counts c_n (n entries): the next gamma step of n uses
+ * rho = (nodetau0 + c_n)^-nodekappa (update_rho_indiv src/snpsamplinge.cc:688-693) */
+void orc_set_counts(orc_state *s, const uint32_t *c);
 /* set_validation_sample src/snpsamplinge.cc:196-224; returns number of locs */
 uint32_t orc_set_validation_sample(orc_state *s, orc_rng *r);
 

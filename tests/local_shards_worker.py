@@ -59,6 +59,47 @@ def match_oracle(ts, world, n, k):
         e.close()
 
 
+def late_state_shards(ts, world, n, k):
+    """the sharded ts_schedule<K, true, WR> from a planted late-training state (tests/late_state.py): gamma_scale = 5e5,
+    gammas at the 1e-8 floor, c_n up to 1e6, lambda of order N"""
+    import late_state
+
+    l, l_eff = 10, 5e5
+    s = late_state.plant(n, l, k, 6500 + k, l_eff=l_eff)
+    orc = op.Oracle(n, l, k, gamma_scale=l_eff)
+    late_state.load_oracle(orc, s)
+    engs = [ts.Engine(n, l, k, device=0, rank=r, world=world, gamma_scale=l_eff) for r in range(world)]
+    for e in engs:
+        late_state.load_engine(e, s)
+    ts.Engine.p2p_connect_local(engs)
+    for e in engs:
+        assert e.launch_info()["kernels_per_snp"] == 0, e.launch_info()   # the sharded whole-schedule kernel
+    train = np.array([3, 3, 7, 1, 7, 0, 2, 5, 9, 4, 4, 6], dtype=np.uint32)
+    val = np.array([0, 1, 2, 4, 6, 8], dtype=np.uint32)
+    for part, hol in ((train, 0), (val, 1), (train[:4], 0)):
+        ts.Engine.run_schedule_all(engs, part, hol_mode=hol)
+        for e in engs:
+            e.synchronize()
+    its = [orc.snp_update(int(x)) for x in train] + [orc.snp_update(int(x), 1) for x in val] + [orc.snp_update(int(x)) for x in train[:4]]
+    g = np.concatenate([e.get_gamma() for e in engs])
+    c = np.concatenate([e.get_counts() for e in engs])
+    assert rel_err(g, orc.gamma()) < 1e-9
+    assert np.array_equal(c, orc.c_indiv())
+    for e in engs:
+        assert rel_err(e.get_lambda(), orc.lambda_()) < 1e-9
+        assert e.total_passes() == sum(its)
+        assert np.array_equal(e.get_lambda(), engs[0].get_lambda())
+        assert e.recoveries() == 0, e.last_error()   # ts_schedule really ran, not its launch-per-pass replay
+    for loc in s.held:
+        parts = [e.heldout_loglik(loc) for e in engs]
+        sm, cnt = sum(p[0] for p in parts), sum(p[1] for p in parts)
+        so, co = orc.heldout_loglik(loc)
+        assert cnt == co and abs(sm - so) <= 1e-10 * abs(so), (loc, sm, so)
+    for e in engs:
+        e.close()
+    orc.close()
+
+
 def deep_queue(ts):
     world, n, l, k = 2, 2000, 1500, 4
     y, _, _ = psd_genotypes(n, l, k, 77, 0.01)
@@ -103,6 +144,8 @@ if __name__ == "__main__":
     what = sys.argv[1]
     if what == "match":
         match_oracle(ts, *(int(x) for x in sys.argv[2:5]))
+    elif what == "late":
+        late_state_shards(ts, *(int(x) for x in sys.argv[2:5]))
     elif what == "deep":
         deep_queue(ts)
     else:

@@ -75,6 +75,7 @@ def lib():
         "orc_set_gamma": (None, [vp, pd]),
         "orc_init_lambda": (None, [vp]),
         "orc_set_lambda": (None, [vp, u32, pd]),
+        "orc_set_counts": (None, [vp, pu]),
         "orc_set_validation_sample": (u32, [vp, C.POINTER(Rng)]),
         "orc_snp_update": (u32, [vp, u32, C.c_int]),
         "orc_pass_partial": (None, [vp, u32, u32, u32, pd]),
@@ -168,6 +169,12 @@ class Oracle:
         lam = np.ascontiguousarray(lam, dtype=np.float64)
         assert lam.shape == (self.k, 2)
         self.L.orc_set_lambda(self.s, loc, _dp(lam))
+
+    def set_counts(self, c):
+        """per-individual update counts c_n: the next gamma step of n uses rho = (nodetau0 + c_n)^-nodekappa"""
+        c = np.ascontiguousarray(c, dtype=np.uint32)
+        assert c.shape == (self.n,)
+        self.L.orc_set_counts(self.s, _up(c))
 
     def _arr(self, fn, shape):
         p = fn(self.s)

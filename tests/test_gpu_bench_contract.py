@@ -107,7 +107,7 @@ def test_bench_two_ranks_json_contract():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    env = dict(os.environ, TSAMD_BENCH_DEVICE="0", GPU_MAX_HW_QUEUES="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, TSAMD_BENCH_DEVICE="0", GPU_MAX_HW_QUEUES="4", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("TSAMD_LIB", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--individuals", "60000", "--pops", "8",

@@ -124,7 +124,8 @@ def test_run_sh_end_to_end(host_bin, tmp_path):
 @pytest.mark.gpu
 def test_run_sh_sharded_over_devices(host_bin, tmp_path):
     """The same command with the individuals sharded (-devices; both shards on device 0 here, one hardware queue each --
-    a shared GPU gives a process two, so more shards than two in one process are not tested on a one-GPU box):
+    of the four a process gets (GPU_MAX_HW_QUEUES=4, HIP's default; fewer can crash the runtime when it replays a captured
+    graph with parallel branches); more shards than two in one process are not tested on a one-GPU box):
     same validation trajectory and stop iteration, theta within the stated tolerance of the
     single-shard run's oracle."""
     data = tmp_path / "data"
@@ -133,7 +134,7 @@ def test_run_sh_sharded_over_devices(host_bin, tmp_path):
         shutil.copy(os.path.join(REF_DATA, f), data / f)
     cmd = [host_bin, "-file", "test.bed", "-n", "200", "-l", "10000", "-k", "3", "-stochastic",
            "-nthreads", "1", "-rfreq", "1000", "-seed", "1234", "-label", "test", "-devices", "0,0"]
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="2")  # shards sharing a device need a hardware queue each
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="4")  # shards sharing a device need a hardware queue each
     r = subprocess.run(cmd, cwd=data, capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     run = data / "n200-k3-l10000-test-seed1234"
