@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "checkpoint.h"
 #include "fast_format.h"
 
 // ---- where the wall clock goes (timing.txt in the run directory; extension) ----------
@@ -34,10 +35,19 @@ struct Stopwatch {
 // file name must land after the earlier one); at most one snapshot waits (128 MB each at N = 1M, K = 8).  drain() returns
 // when every file handed over is complete and closed: before the process exits, on every path (stop rule, SIGTERM,
 // -max-iter, an error).
+// A job of the checkpoint kind (-checkpoint: ckpt_path is set) also carries the engine state the main thread exported at
+// the same iteration -- the location part of context 0 and every shard's individual part -- and the host's own state;
+// the writer joins the shards' parts and writes checkpoint.bin after gamma.txt / theta.txt (host/checkpoint.h: to a
+// .tmp name, then renamed).  It is the same job, so the one-snapshot rule and drain() cover it.
 struct SaveJob {
   std::string gamma_path, theta_path;
   std::vector<double> g, t;
   size_t n = 0, k = 0;
+  std::string ckpt_path;  // empty: no checkpoint with this save
+  ckpt::FileHeader ckpt_head{};
+  ckpt::HostState ckpt_host{};
+  ckpt::Buf ckpt_loc;
+  std::vector<ckpt::Buf> ckpt_indiv;  // rank order
 };
 class ModelWriter {
  public:
@@ -98,7 +108,16 @@ class ModelWriter {
     ok = (fclose(f) == 0) && ok;
     ok = (fclose(h) == 0) && ok;
     if (!ok) *err = std::string("error writing gamma/theta file:") + strerror(errno);
-    return ok;
+    return ok && write_checkpoint(j, err);
+  }
+  static bool write_checkpoint(const SaveJob &j, std::string *err) {
+    if (j.ckpt_path.empty()) return true;
+    if (j.ckpt_indiv.size() == 1)  // one shard: its part is the global one
+      return ckpt::write_file(j.ckpt_path, j.ckpt_head, j.ckpt_host, j.ckpt_loc.data(), j.ckpt_loc.size(), j.ckpt_indiv[0].data(),
+                              j.ckpt_indiv[0].size(), err);
+    ckpt::Buf all;
+    return ckpt::merge_indiv(j.ckpt_indiv, &all, err) &&
+           ckpt::write_file(j.ckpt_path, j.ckpt_head, j.ckpt_host, j.ckpt_loc.data(), j.ckpt_loc.size(), all.data(), all.size(), err);
   }
   static bool write_matrix(FILE *f, const double *v, size_t n, size_t k) {
     const size_t rows_per_block = std::max<size_t>(1, (size_t)(1u << 20) / (k * 24 + 1));

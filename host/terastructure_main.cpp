@@ -38,11 +38,23 @@
 #include <string>
 #include <vector>
 
+#include "checkpoint.h"
 #include "fast_format.h"
 #include "model_writer.h"
 #include "tsamd.h"
 
 namespace {
+
+// host/checkpoint.h carries the engine's blob header under its own name (it is built without libtsamd's header)
+static_assert(sizeof(ckpt::BlobHeader) == sizeof(tsamd_state_header) && offsetof(ckpt::BlobHeader, part) == offsetof(tsamd_state_header, part) &&
+                  offsetof(ckpt::BlobHeader, shard_begin) == offsetof(tsamd_state_header, shard_begin) &&
+                  offsetof(ckpt::BlobHeader, alpha) == offsetof(tsamd_state_header, alpha) &&
+                  offsetof(ckpt::BlobHeader, payload_bytes) == offsetof(tsamd_state_header, payload_bytes) &&
+                  offsetof(ckpt::BlobHeader, checksum) == offsetof(tsamd_state_header, checksum),
+              "ckpt::BlobHeader mirrors tsamd_state_header");
+static_assert(ckpt::kBlobMagic == TSAMD_STATE_MAGIC && ckpt::kBlobVersion == TSAMD_STATE_VERSION && ckpt::kPartIndiv == TSAMD_STATE_PART_INDIV &&
+                  ckpt::kPartLoc == TSAMD_STATE_PART_LOC,
+              "blob constants of include/tsamd.h");
 
 // ---- GSL-compatible random numbers (gsl_rng_mt19937 / gsl_rng_uniform_int /
 // gsl_ran_gamma; the unit normal uses the polar Box-Muller method) -----
@@ -132,11 +144,15 @@ struct Options {
   uint32_t max_iter = 0;  // extension: stop after this many iterations (0 = reference behaviour)
   unsigned ingest_threads = 0;  // extension: reader threads of the .bed ingest (0 = up to 8)
   bool ingest_only = false;     // extension: read the genotypes into HBM, write param.txt, stop (ingest measurement)
+  bool checkpoint = false;      // extension: every save_model after the initial one also writes <run dir>/checkpoint.bin
+  std::string resume;           // extension: start from this checkpoint.bin instead of init_gamma
 };
 
 struct Timing {
   double ingest = 0, validation_sample = 0, init_gamma = 0, training = 0, report = 0, save_blocking = 0, save_writer = 0, save_wait = 0;
-  uint32_t reports = 0, saves = 0;
+  double ckpt_blocking = 0, ckpt_first = 0, resume = 0;  // of save_blocking: exporting the engine state for checkpoint.bin; reading and importing one
+  uint64_t ckpt_bytes = 0;
+  uint32_t reports = 0, saves = 0, ckpts = 0;
 };
 
 struct Run {
@@ -154,6 +170,7 @@ struct Run {
   // stop rule state (src/snpsamplinge.cc:26-31)
   double prev_h = -2147483647, max_h = -2147483647;
   uint32_t nh = 0;
+  Mt19937 *rng = nullptr;  // the run's generator (its state goes into checkpoint.bin)
   std::string bed_path;
   std::vector<std::string> labels;      // -idfile: individual labels, echoed into gammasave.txt
   std::vector<uint8_t> text_payload;   // .012 input: the columns re-packed as PLINK codes, kept for read_column
@@ -239,7 +256,48 @@ void set_gamma_all(Run &r, const std::vector<double> &g) {
   }
 }
 
+// ---- pinned host memory for the checkpoint snapshots (-checkpoint) ----------------------
+// tsamd_state_export fills a buffer of tsamd_host_alloc by one DMA, without the staging copy a pageable one takes.  Pinning
+// hundreds of megabytes costs more than the copy it saves, so a buffer the writer thread is done with comes back here and
+// the next snapshot takes it: a run pins as many as are in flight at once (one being filled, one waiting, one being
+// written) and no more.  get() is the main thread's, put() the writer thread's.
+struct PinnedPool {
+  std::mutex mu;
+  std::vector<std::pair<void *, size_t>> idle;
+  static PinnedPool &the() {
+    static PinnedPool p;
+    return p;
+  }
+  static void *get(size_t bytes) {
+    PinnedPool &p = the();
+    {
+      std::lock_guard<std::mutex> lk(p.mu);
+      for (size_t i = 0; i < p.idle.size(); ++i)
+        if (p.idle[i].second == bytes) {
+          void *ptr = p.idle[i].first;
+          p.idle.erase(p.idle.begin() + (long)i);
+          return ptr;
+        }
+    }
+    void *ptr = nullptr;
+    return tsamd_host_alloc(&ptr, bytes) == 0 ? ptr : nullptr;
+  }
+  static void put(void *ptr, size_t bytes) {
+    PinnedPool &p = the();
+    std::lock_guard<std::mutex> lk(p.mu);
+    p.idle.emplace_back(ptr, bytes);
+  }
+  static void clear() {  // (after the writer has drained: every buffer is back)
+    PinnedPool &p = the();
+    std::lock_guard<std::mutex> lk(p.mu);
+    for (auto &b : p.idle) tsamd_host_free(b.first);
+    p.idle.clear();
+  }
+};
+const ckpt::BufSource kPinned = {PinnedPool::get, PinnedPool::put};
+
 void destroy_all(Run &r) {
+  PinnedPool::clear();
   for (tsamd_ctx *c : r.ctxs) tsamd_destroy(c);
   r.ctxs.clear();
   r.ctx = nullptr;
@@ -264,7 +322,12 @@ void usage() {
           "\t-device <id>\t HIP device ordinal (default 0)\n"
           "\t-devices <a,b,..>\t shard the individuals over these HIP devices (one shard each)\n"
           "\t-ingest-threads <T>\t reader threads of the .bed ingest (default: up to 8)\n"
-          "\t-ingest-only\t read the genotypes into HBM, report the rate, write param.txt and stop\n");
+          "\t-ingest-only\t read the genotypes into HBM, report the rate, write param.txt and stop\n"
+          "\t-checkpoint\t with every gamma.txt / theta.txt after the initial one, also write <run dir>/checkpoint.bin:\n"
+          "\t\t\t the full engine and sampler state of that iteration\n"
+          "\t-resume <file>\t continue the run that wrote this checkpoint.bin (same -n -l -k -seed -rfreq and data; any\n"
+          "\t\t\t -devices); with the same device count the continuation is bit for bit the uninterrupted\n"
+          "\t\t\t run's.  Not together with -compute-beta\n");
   fflush(stdout);
 }
 
@@ -331,6 +394,8 @@ void setup_run_dir(Run &r) {
   r.plog_u("blocks", blocks);
   r.plog_b("compute_beta", o.compute_beta);
   r.plog_d("stop_threshold", o.stop_threshold);
+  r.plog_b("checkpoint", o.checkpoint);
+  fprintf(r.plog, "resume: %s\n", o.resume.empty() ? "False" : o.resume.c_str()), fflush(r.plog);
   const std::string nd = r.file_str("/network.dat");
   unlink(nd.c_str());
   if (symlink(o.datfname.c_str(), nd.c_str()) < 0) fprintf(stderr, "warning: cannot symlink %s\n", nd.c_str());
@@ -642,7 +707,7 @@ std::string add_iter_suffix(const Run &r, const char *c) {
 // save_gamma (src/snpsamplinge.cc:546-576)
 // The main thread snapshots gamma / theta; the writer thread formats and writes them (ModelWriter above) while the next
 // schedules run.  The file names are fixed here (-file-suffix: the iteration of THIS save).
-void save_model(Run &r) {
+void save_model(Run &r, bool with_checkpoint = true) {
   Stopwatch sw;
   const size_t n = r.o.n, k = r.o.k;
   std::unique_ptr<SaveJob> job(new SaveJob);
@@ -657,6 +722,36 @@ void save_model(Run &r) {
     shard_span(r, i, b, c);
     TS(r, tsamd_get_gamma(r.ctxs[i], job->g.data() + (size_t)b * k));
     TS(r, tsamd_get_theta(r.ctxs[i], job->t.data() + (size_t)b * k));
+  }
+  if (r.o.checkpoint && with_checkpoint) {
+    // the whole engine state of this iteration, next to gamma.txt: the location part from context 0 (identical on every
+    // shard), every shard's own part, the sampler and the stop rule.  Exported here, written by the writer thread.
+    Stopwatch cw;
+    job->ckpt_path = r.file_str("/checkpoint.bin");
+    ckpt::FileHeader &fh = job->ckpt_head;
+    fh.n = r.o.n, fh.l = r.o.l, fh.k = r.o.k, fh.rfreq = r.o.rfreq, fh.nparts = (uint32_t)r.ctxs.size();
+    fh.seed = r.o.seed, fh.stop_threshold = r.o.stop_threshold;
+    ckpt::HostState &hs = job->ckpt_host;
+    hs.iter = r.iter, hs.nh = r.nh, hs.prev_h = r.prev_h, hs.max_h = r.max_h;
+    memcpy(hs.mt, r.rng->mt, sizeof hs.mt);
+    hs.mti = r.rng->mti;
+    job->ckpt_indiv.resize(r.ctxs.size());
+    for (size_t i = 0; i < r.ctxs.size(); ++i) {
+      uint64_t ib = 0, lb = 0;
+      r.ctx = r.ctxs[i];
+      TS(r, tsamd_state_sizes(r.ctxs[i], &ib, &lb));
+      if (!job->ckpt_indiv[i].alloc(ib, &kPinned) || (i == 0 && !job->ckpt_loc.alloc(lb, &kPinned))) {
+        r.lerr("checkpoint: %s\n", tsamd_last_error(nullptr));
+        fprintf(stderr, "error: checkpoint: %s\n", tsamd_last_error(nullptr));
+        exit(-1);
+      }
+      TS(r, tsamd_state_export(r.ctxs[i], job->ckpt_indiv[i].data(), ib, i == 0 ? job->ckpt_loc.data() : nullptr, i == 0 ? lb : 0));
+      r.tm.ckpt_bytes += ib + (i == 0 ? lb : 0);
+    }
+    r.ctx = r.ctxs[0];
+    const double took = cw.lap();
+    r.tm.ckpt_blocking += took;
+    if (r.tm.ckpts++ == 0) r.tm.ckpt_first = took;  // (it pins its buffers; later ones take them back from the writer)
   }
   double waited = 0;
   if (!r.writer.submit(std::move(job), &waited)) {
@@ -693,6 +788,10 @@ void write_timing(Run &r) {
           t.init_gamma, t.training, t.report, t.reports);
   fprintf(f, "save_model, main thread blocked: %.3f (%u saves; of which waiting for the writer: %.3f)\n", t.save_blocking, t.saves, t.save_wait);
   fprintf(f, "save_model, writer thread busy (overlapped with training): %.3f\n", t.save_writer);
+  if (r.o.checkpoint)
+    fprintf(f, "checkpoint, main thread blocked (part of save_model's): %.3f (%u checkpoints, %.1f MB of engine state each; the first, which pins its buffers: %.3f)\n",
+            t.ckpt_blocking, t.ckpts, t.ckpts ? (double)t.ckpt_bytes / t.ckpts / 1e6 : 0.0, t.ckpt_first);
+  if (!r.o.resume.empty()) fprintf(f, "resume (read, validate, import): %.3f\n", t.resume);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
@@ -956,6 +1055,10 @@ int main(int argc, char **argv) {
       o.ingest_threads = (unsigned)atoi(need(a));
     } else if (!strcmp(a, "-ingest-only")) {
       o.ingest_only = true;
+    } else if (!strcmp(a, "-checkpoint")) {
+      o.checkpoint = true;
+    } else if (!strcmp(a, "-resume")) {
+      o.resume = need(a);
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -969,6 +1072,26 @@ int main(int argc, char **argv) {
   if (o.loadcmp) {
     fprintf(stdout, "+ loadcmp option set: nothing to do\n");
     return 0;
+  }
+
+  // -resume: the file is read and checked against the flags before anything else exists -- a checkpoint of another run,
+  // a truncated or a corrupt one is refused with nothing written (the engine validates its parts once more on import)
+  ckpt::FileHeader resume_head{};
+  ckpt::HostState resume_host{};
+  ckpt::Buf resume_loc, resume_indiv;
+  Stopwatch resume_sw;
+  if (!o.resume.empty()) {
+    if (o.compute_beta) {
+      fprintf(stderr, "error: -resume continues a training run; it does not go with -compute-beta\n");
+      return -1;
+    }
+    std::string why;
+    const ckpt::Expect want{o.n, o.l, o.k, o.rfreq, o.seed};
+    if (!ckpt::read_file(o.resume, want, &resume_head, &resume_host, &resume_loc, &resume_indiv, &why)) {
+      fprintf(stderr, "error: -resume: %s\n", why.c_str());
+      return -1;
+    }
+    r.tm.resume = resume_sw.lap();
   }
 
   // the GPU context comes first so that a missing device fails before any output exists
@@ -1023,6 +1146,7 @@ int main(int argc, char **argv) {
 
   Mt19937 rng(0);  // gsl_rng_alloc: default seed 0 -> 4357
   if (o.seed) rng.set((unsigned long)o.seed);
+  r.rng = &rng;
   unlink(r.file_str("/likelihood-analysis.txt").c_str());
   r.vf = fopen(r.file_str("/validation.txt").c_str(), "w");
   if (!r.vf) {
@@ -1069,20 +1193,52 @@ int main(int argc, char **argv) {
   phase.lap();
   set_validation_sample(r, rng);
   r.tm.validation_sample = phase.lap();
-  {  // init_gamma (:226-237): n-major, k inner, Gamma(100 v, 0.01)
-    std::vector<double> g((size_t)o.n * o.k);
-    for (size_t i = 0; i < g.size(); ++i) {
-      const double v = (o.k < 100) ? 1.0 : (double)100.0 / o.k;
-      g[i] = rng.gamma(100 * v, 0.01);
+  if (!o.resume.empty()) {
+    // instead of init_gamma, the initial likelihood and the initial save: the engine state of the file into every shard
+    // (the location part as it is, the shard's slice of the global individual part), then the host's own -- the
+    // generator's state replaces the one the validation sample has just advanced (the sample itself is a function of
+    // the seed and the data: it came out as in the run that wrote the file)
+    resume_sw.lap();
+    for (size_t i = 0; i < r.ctxs.size(); ++i) {
+      uint32_t b, c;
+      shard_span(r, i, b, c);
+      ckpt::Buf part;
+      std::string why;
+      if (!ckpt::slice_indiv(resume_indiv.data(), resume_indiv.size(), b, c, &part, &why)) {
+        fprintf(stderr, "error: -resume: %s\n", why.c_str());
+        exit(-1);
+      }
+      r.ctx = r.ctxs[i];
+      TS(r, tsamd_state_import(r.ctxs[i], part.data(), part.size(), resume_loc.data(), resume_loc.size()));
     }
-    set_gamma_all(r, g);
+    r.ctx = r.ctxs[0];
+    r.iter = resume_host.iter;
+    r.nh = resume_host.nh;
+    r.prev_h = resume_host.prev_h;
+    r.max_h = resume_host.max_h;
+    memcpy(rng.mt, resume_host.mt, sizeof rng.mt);
+    rng.mti = resume_host.mti;
+    r.tm.resume += resume_sw.lap();
+    r.lerr("resumed from %s at iteration %u", o.resume.c_str(), r.iter);
+    printf("+ resumed from %s at iteration %u\n", o.resume.c_str(), r.iter);
+    resume_loc.alloc(0);
+    resume_indiv.alloc(0);
+  } else {
+    {  // init_gamma (:226-237): n-major, k inner, Gamma(100 v, 0.01)
+      std::vector<double> g((size_t)o.n * o.k);
+      for (size_t i = 0; i < g.size(); ++i) {
+        const double v = (o.k < 100) ? 1.0 : (double)100.0 / o.k;
+        g[i] = rng.gamma(100 * v, 0.01);
+      }
+      set_gamma_all(r, g);
+    }
+    r.tm.init_gamma = phase.lap();
+    printf("+ computing initial heldout likelihood\n");
+    compute_likelihood(r, true);
+    r.tm.report += phase.lap();
+    r.tm.reports++;
+    save_model(r, false);  // (the initial state: nothing to resume from yet)
   }
-  r.tm.init_gamma = phase.lap();
-  printf("+ computing initial heldout likelihood\n");
-  compute_likelihood(r, true);
-  r.tm.report += phase.lap();
-  r.tm.reports++;
-  save_model(r);
   printf("\n+ computing initial training likelihood\n+ done..\n+ initialization end\n");
   fflush(stdout);
 

@@ -222,6 +222,56 @@ int tsamd_p2p_connect_local(tsamd_ctx *const *ctxs, uint32_t count);
  * like tsamd_run_schedule; follow with tsamd_synchronize on each context. */
 int tsamd_run_schedule_all(tsamd_ctx *const *ctxs, uint32_t count, const uint32_t *locs, uint32_t n, int hol_mode);
 
+/* ---- the full engine state: save, restore, resume ------------------------------------------
+ * Everything a later call depends on, so that export -> (file, new process, new context) -> import is a cut of the
+ * schedule like any other: bit for bit invisible in a given launch mode.  Two blobs ("parts"), each a
+ * tsamd_state_header followed by its payload:
+ *  - the INDIV part, this shard's own: gamma[shard_count][k] doubles, then w[shard_count][k] doubles -- the stored
+ *    exp(Elogtheta) up to a per-individual factor, AS IT IS in HBM: the kernel families scale it differently, so it cannot be
+ *    re-derived from gamma -- then c_n[shard_count] uint32, zero-padded to a multiple of 8 bytes.  Rows ascending, unpadded:
+ *    the parts of all shards concatenate into the global arrays and re-slice on tsamd_shard_range boundaries.
+ *  - the LOC part, identical on every rank of a sharded run (shard_begin = 0, shard_count = n in its header):
+ *    lambda[l][k][2] doubles, then eb[l][k][2] doubles (the stored exp(Elogbeta)), then tsamd_state_pending followed by
+ *    lam[2k] and eb[2k] doubles (the pending gamma step: the last update's location, whether it was a validation-mode one,
+ *    its passes, and the exp(Elogbeta) its last pass used), then total_passes (uint64) and the pass histogram
+ *    (TSAMD_PASS_HIST_BINS uint64).
+ * Not state, the restored context keeps its own: exchange tags, epochs, parities, graphs, the launch mode, held-out folds
+ * (register them before or after the import: they live in the genotype columns) and the genotypes themselves.
+ * checksum: FNV-1a over the payload taken as little-endian 64-bit words (h = 14695981039346656037; per word h ^= word,
+ * h *= 1099511628211) -- against truncation, not against attackers.  All fields little-endian, as the GPU's host. */
+#define TSAMD_STATE_MAGIC 0x54534d54u /* "TMST" */
+#define TSAMD_STATE_VERSION 1u
+#define TSAMD_STATE_PART_INDIV 1u
+#define TSAMD_STATE_PART_LOC 2u
+typedef struct tsamd_state_header { /* 128 bytes */
+  uint32_t magic, version, part;
+  uint32_t n, l, k, shard_begin, shard_count;
+  uint32_t max_inner, reserved0;
+  double alpha, eta0, eta1, nodetau0, nodekappa, conv_thresh, gamma_scale; /* the model constants of tsamd_config */
+  uint64_t payload_bytes; /* bytes after this header */
+  uint64_t checksum;      /* of the payload */
+  uint64_t reserved1[2];
+} tsamd_state_header;
+typedef struct tsamd_state_pending { /* 32 bytes; lam[2k] and eb[2k] doubles follow */
+  uint32_t valid; /* an update has run since creation / tsamd_clear_pending: its gamma step is pending unless hol */
+  uint32_t loc, hol, iters;
+  uint32_t done; /* always 1 when valid: a context is exported between calls, whole updates only */
+  uint32_t reserved[3];
+} tsamd_state_pending;
+/* bytes of the two parts for this context (either pointer may be NULL) */
+int tsamd_state_sizes(tsamd_ctx *ctx, uint64_t *indiv_bytes, uint64_t *loc_bytes);
+/* Synchronous; settles the context first like every getter (a recovered schedule is exported after its replay).  Either
+ * pointer may be NULL with a zero byte count: only the other part is written.  The byte counts must be those of
+ * tsamd_state_sizes.  Buffers from tsamd_host_alloc receive their part by DMA without a staging copy. */
+int tsamd_state_export(tsamd_ctx *ctx, void *indiv, uint64_t indiv_bytes, void *loc, uint64_t loc_bytes);
+/* Validates both parts before it touches anything: TSAMD_EINVAL, a message that names the field, and an unchanged context
+ * for a bad magic / version / part, n, l, k, shard or model constant that differs from the context's, a wrong byte count, a
+ * bad checksum, or a value the setters would refuse (gamma not finite or below 1e-8, w negative or not finite, lambda / eb
+ * not positive and finite, iters > max_inner, loc >= l, a record that is valid but not done).  On success replaces gamma, w,
+ * c_n (padding individuals as tsamd_create leaves them), lambda, eb, the pending record and the counters.  Either pointer
+ * may be NULL with a zero byte count: only the other part is restored. */
+int tsamd_state_import(tsamd_ctx *ctx, const void *indiv, uint64_t indiv_bytes, const void *loc, uint64_t loc_bytes);
+
 /* ---- measurement / synthetic workloads ---------------------------------------- */
 /* Pritchard-Stephens-Donnelly genotypes straight into HBM for columns
  * [first_loc, first_loc + n_locs): y ~ Binomial(2, sum_k theta[n][k] * beta[j][k]),

@@ -97,6 +97,8 @@ struct tsamd_ctx {
   uint32_t sched_cap = 0;
   uint8_t *h_stage = nullptr;  // pinned staging for uploads
   size_t stage_bytes = 0;
+  double *d_state = nullptr;  // device staging of tsamd_state_export / _import (the individual part), kept between calls
+  size_t state_bytes = 0;
   std::map<uint32_t, HeldLoc> held;
   // flat device copy of the held-out table (ids + true genotypes, locations ascending), rebuilt
   // lazily after tsamd_set_heldout / a re-upload; spans index it by location
@@ -737,6 +739,7 @@ void tsamd_destroy(tsamd_ctx *c) {
   hipFree(c->d_fold_orig);
   hipFree(c->d_hsums);
   if (c->h_stage) hipHostFree(c->h_stage);
+  hipFree(c->d_state);
   for (auto &j : c->journal) {
     hipHostFree(j.ent);
     if (j.done) hipEventDestroy(j.done);
@@ -2104,6 +2107,328 @@ int tsamd_recoveries(tsamd_ctx *c, uint32_t *count) {
   CHECK_CTX(c);
   if (!count) return fail(c, TSAMD_EINVAL, "null output");
   *count = c->recoveries;
+  return TSAMD_OK;
+}
+
+// ---- tsamd_state_sizes / _export / _import --------------------------------------------------------------------------
+static_assert(sizeof(tsamd_state_header) == 128 && sizeof(tsamd_state_pending) == 32, "blob layouts of include/tsamd.h");
+
+static uint64_t state_checksum(const void *data, uint64_t bytes) {  // FNV-1a over 64-bit words (bytes is a multiple of 8)
+  uint64_t h = 14695981039346656037ull;
+  const uint8_t *p = (const uint8_t *)data;
+  for (uint64_t i = 0; i + 8 <= bytes; i += 8) {
+    uint64_t wd;
+    memcpy(&wd, p + i, 8);
+    h = (h ^ wd) * 1099511628211ull;
+  }
+  return h;
+}
+
+static uint64_t state_indiv_payload(const tsamd_ctx *c) {
+  return (uint64_t)2 * c->n_local * c->cfg.k * sizeof(double) + ((uint64_t)c->n_local * sizeof(uint32_t) + 7u) / 8u * 8u;
+}
+static uint64_t state_loc_payload(const tsamd_ctx *c) {
+  const uint64_t J = 2 * (uint64_t)c->cfg.k;
+  return (uint64_t)2 * c->cfg.l * J * sizeof(double) + sizeof(tsamd_state_pending) + 2 * J * sizeof(double) + sizeof(uint64_t) +
+         (uint64_t)TSAMD_PASS_HIST_BINS * sizeof(uint64_t);
+}
+
+static void state_fill_header(const tsamd_ctx *c, uint32_t part, uint64_t payload, tsamd_state_header *h) {
+  memset(h, 0, sizeof *h);
+  h->magic = TSAMD_STATE_MAGIC;
+  h->version = TSAMD_STATE_VERSION;
+  h->part = part;
+  h->n = c->cfg.n;
+  h->l = c->cfg.l;
+  h->k = c->cfg.k;
+  h->shard_begin = part == TSAMD_STATE_PART_INDIV ? c->n_begin : 0u;
+  h->shard_count = part == TSAMD_STATE_PART_INDIV ? c->n_local : c->cfg.n;
+  h->max_inner = c->cfg.max_inner;
+  h->alpha = c->cfg.alpha;
+  h->eta0 = c->cfg.eta0;
+  h->eta1 = c->cfg.eta1;
+  h->nodetau0 = c->cfg.nodetau0;
+  h->nodekappa = c->cfg.nodekappa;
+  h->conv_thresh = c->cfg.conv_thresh;
+  h->gamma_scale = c->cfg.gamma_scale;
+  h->payload_bytes = payload;
+}
+
+// header of a part handed to tsamd_state_import against what this context would export
+static int state_check_header(tsamd_ctx *c, const char *name, uint32_t part, const void *blob, uint64_t bytes, uint64_t payload) {
+  if (bytes < sizeof(tsamd_state_header)) return fail(c, TSAMD_EINVAL, "state import: the %s part is shorter than its header (%llu bytes)", name, (unsigned long long)bytes);
+  tsamd_state_header h, want;
+  memcpy(&h, blob, sizeof h);
+  state_fill_header(c, part, payload, &want);
+  if (h.magic != want.magic) return fail(c, TSAMD_EINVAL, "state import: bad magic %08x in the %s part", h.magic, name);
+  if (h.version != want.version) return fail(c, TSAMD_EINVAL, "state import: format version %u of the %s part is not %u", h.version, name, want.version);
+  if (h.part != want.part) return fail(c, TSAMD_EINVAL, "state import: part %u was given as the %s part (%u)", h.part, name, want.part);
+#define STATE_FIELD_U(f) \
+  if (h.f != want.f) return fail(c, TSAMD_EINVAL, "state import: " #f " = %u in the %s part, %u in the context", h.f, name, want.f)
+#define STATE_FIELD_D(f) \
+  if (memcmp(&h.f, &want.f, sizeof(double)) != 0) return fail(c, TSAMD_EINVAL, "state import: " #f " = %.17g in the %s part, %.17g in the context", h.f, name, want.f)
+  STATE_FIELD_U(n);
+  STATE_FIELD_U(l);
+  STATE_FIELD_U(k);
+  STATE_FIELD_U(shard_begin);
+  STATE_FIELD_U(shard_count);
+  STATE_FIELD_U(max_inner);
+  STATE_FIELD_D(alpha);
+  STATE_FIELD_D(eta0);
+  STATE_FIELD_D(eta1);
+  STATE_FIELD_D(nodetau0);
+  STATE_FIELD_D(nodekappa);
+  STATE_FIELD_D(conv_thresh);
+  STATE_FIELD_D(gamma_scale);
+#undef STATE_FIELD_U
+#undef STATE_FIELD_D
+  if (h.payload_bytes != payload || bytes != sizeof h + payload)
+    return fail(c, TSAMD_EINVAL, "state import: byte count of the %s part: header says %llu payload bytes, %llu were given, the context needs %llu",
+                name, (unsigned long long)h.payload_bytes, (unsigned long long)(bytes - sizeof h), (unsigned long long)payload);
+  if (state_checksum((const uint8_t *)blob + sizeof h, payload) != h.checksum)
+    return fail(c, TSAMD_EINVAL, "state import: checksum of the %s part does not match its payload", name);
+  return TSAMD_OK;
+}
+
+static bool state_is_pinned(const void *ptr) {
+  hipPointerAttribute_t attr;
+  const bool pinned = hipPointerGetAttributes(&attr, ptr) == hipSuccess && attr.type == hipMemoryTypeHost;
+  if (!pinned) (void)hipGetLastError();  // (an unknown pointer is reported as an error: pageable memory)
+  return pinned;
+}
+
+// device <-> host copies of a part's payload: one DMA when the host buffer is pinned (tsamd_host_alloc), otherwise
+// through the context's two pinned staging halves, the host copy of one piece overlapping the DMA of the next
+static int state_copy(tsamd_ctx *c, void *host, void *dev, uint64_t bytes, bool to_host) {
+  if (bytes == 0) return TSAMD_OK;
+  if (state_is_pinned(host)) {
+    HIP_TRY(c, to_host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream) : hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return TSAMD_OK;
+  }
+  const uint64_t half = std::min<uint64_t>(bytes, (uint64_t)32 << 20);
+  if (int rc = ensure_stage(c, 2 * half)) return rc;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreateWithFlags(&ev[0], hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[1], hipEventDisableTiming);
+  const uint64_t pieces = (bytes + half - 1) / half;
+  auto len = [&](uint64_t i) { return std::min<uint64_t>(half, bytes - i * half); };
+  if (to_host) {
+    for (uint64_t i = 0; i <= pieces && e == hipSuccess; ++i) {  // DMA of piece i in flight while piece i - 1 is copied out
+      if (i < pieces) {
+        e = hipMemcpyAsync(c->h_stage + (i & 1) * half, (uint8_t *)dev + i * half, len(i), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(ev[i & 1], c->stream);
+      }
+      if (i > 0 && e == hipSuccess) {
+        e = hipEventSynchronize(ev[(i - 1) & 1]);
+        if (e == hipSuccess) memcpy((uint8_t *)host + (i - 1) * half, c->h_stage + ((i - 1) & 1) * half, len(i - 1));
+      }
+    }
+  } else {
+    for (uint64_t i = 0; i < pieces && e == hipSuccess; ++i) {
+      if (i >= 2) e = hipEventSynchronize(ev[i & 1]);  // this half's previous DMA
+      if (e != hipSuccess) break;
+      memcpy(c->h_stage + (i & 1) * half, (const uint8_t *)host + i * half, len(i));
+      e = hipMemcpyAsync((uint8_t *)dev + i * half, c->h_stage + (i & 1) * half, len(i), hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipEventRecord(ev[i & 1], c->stream);
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (ev[0]) hipEventDestroy(ev[0]);
+  if (ev[1]) hipEventDestroy(ev[1]);
+  if (e != hipSuccess) return fail(c, TSAMD_EHIP, "state copy: %s", hipGetErrorString(e));
+  return TSAMD_OK;
+}
+
+// the device staging buffer of the individual part: allocated by the first export or import and kept (a hipFree per
+// call would synchronise the whole device, which other shards may share); tsamd_destroy frees it
+static int ensure_state_stage(tsamd_ctx *c, size_t bytes) {
+  if (c->state_bytes >= bytes) return TSAMD_OK;
+  hipFree(c->d_state);
+  c->d_state = nullptr;
+  c->state_bytes = 0;
+  HIP_TRY(c, hipMalloc((void **)&c->d_state, bytes));
+  c->state_bytes = bytes;
+  return TSAMD_OK;
+}
+
+// the slot of Ctl::st the next kernel of the sequence reads (it was written by the last one: parity (q - 1) & 1; a fresh
+// context's first kernel has parity 0 and reads slot 1, zeroed by tsamd_create)
+static uint32_t state_live_slot(const tsamd_ctx *c) { return (uint32_t)(c->q & 1u) ^ 1u; }
+
+int tsamd_state_sizes(tsamd_ctx *c, uint64_t *indiv_bytes, uint64_t *loc_bytes) {
+  CHECK_CTX(c);
+  if (indiv_bytes) *indiv_bytes = sizeof(tsamd_state_header) + state_indiv_payload(c);
+  if (loc_bytes) *loc_bytes = sizeof(tsamd_state_header) + state_loc_payload(c);
+  return TSAMD_OK;
+}
+
+int tsamd_state_export(tsamd_ctx *c, void *indiv, uint64_t indiv_bytes, void *loc, uint64_t loc_bytes) {
+  CHECK_CTX(c);
+  SETTLE(c);
+  if ((indiv == nullptr) != (indiv_bytes == 0) || (loc == nullptr) != (loc_bytes == 0))
+    return fail(c, TSAMD_EINVAL, "state export: a NULL part goes with a zero byte count and only with it");
+  const uint64_t ip = state_indiv_payload(c), lp = state_loc_payload(c);
+  if (indiv && indiv_bytes != sizeof(tsamd_state_header) + ip)
+    return fail(c, TSAMD_EINVAL, "state export: the indiv part takes %llu bytes, %llu given", (unsigned long long)(sizeof(tsamd_state_header) + ip), (unsigned long long)indiv_bytes);
+  if (loc && loc_bytes != sizeof(tsamd_state_header) + lp)
+    return fail(c, TSAMD_EINVAL, "state export: the loc part takes %llu bytes, %llu given", (unsigned long long)(sizeof(tsamd_state_header) + lp), (unsigned long long)loc_bytes);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t K = c->cfg.k;
+  if (indiv) {
+    uint8_t *pay = (uint8_t *)indiv + sizeof(tsamd_state_header);
+    if (int rc = ensure_state_stage(c, ip)) return rc;
+    double *d_stage = c->d_state;
+    const uint32_t TN = state_tile(K);
+    hipError_t e = hipMemsetAsync((uint8_t *)d_stage + ip - 8, 0, 8, c->stream);  // (the zero padding behind an odd number of c_n)
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(ts_state_pack, dim3((c->n_local + TN - 1) / TN, 2), dim3(256), (size_t)K * (TN + 1) * sizeof(double), c->stream,
+                         c->p.gam, c->p.w, c->p.cnt, c->npad, K, c->n_local, TN, d_stage);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(c, TSAMD_EHIP, "state export: %s", hipGetErrorString(e));
+    if (int rc = state_copy(c, pay, d_stage, ip, true)) return rc;
+    tsamd_state_header h;
+    state_fill_header(c, TSAMD_STATE_PART_INDIV, ip, &h);
+    h.checksum = state_checksum(pay, ip);
+    memcpy(indiv, &h, sizeof h);
+  }
+  if (loc) {
+    uint8_t *pay = (uint8_t *)loc + sizeof(tsamd_state_header);
+    const uint64_t J = 2 * (uint64_t)K, arr = (uint64_t)c->cfg.l * J * sizeof(double);
+    if (int rc = state_copy(c, pay, c->p.lam, arr, true)) return rc;
+    if (int rc = state_copy(c, pay + arr, c->p.eb, arr, true)) return rc;
+    // the pending record: the live slot as the last kernel left it -- what the next call's first pass reads (a whole
+    // update, done: ts_flush and the whole-schedule kernels complete the last pass before a call ends) -- and the counters
+    State st;
+    unsigned long long counters[1 + TSAMD_PASS_HIST_BINS];
+    HIP_TRY(c, hipMemcpyAsync(&st, &c->p.ctl->st[state_live_slot(c)], sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counters, &c->p.ctl->total_passes, sizeof counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    tsamd_state_pending pr;
+    memset(&pr, 0, sizeof pr);
+    pr.valid = st.valid;
+    pr.loc = st.loc;
+    pr.hol = st.hol;
+    pr.iters = st.iters;
+    pr.done = st.done;
+    uint8_t *q = pay + 2 * arr;
+    memcpy(q, &pr, sizeof pr);
+    memcpy(q + sizeof pr, st.lam, J * sizeof(double));
+    memcpy(q + sizeof pr + J * sizeof(double), st.eb, J * sizeof(double));
+    memcpy(q + sizeof pr + 2 * J * sizeof(double), counters, sizeof counters);
+    tsamd_state_header h;
+    state_fill_header(c, TSAMD_STATE_PART_LOC, lp, &h);
+    h.checksum = state_checksum(pay, lp);
+    memcpy(loc, &h, sizeof h);
+  }
+  return TSAMD_OK;
+}
+
+int tsamd_state_import(tsamd_ctx *c, const void *indiv, uint64_t indiv_bytes, const void *loc, uint64_t loc_bytes) {
+  CHECK_CTX(c);
+  SETTLE(c);
+  if ((indiv == nullptr) != (indiv_bytes == 0) || (loc == nullptr) != (loc_bytes == 0))
+    return fail(c, TSAMD_EINVAL, "state import: a NULL part goes with a zero byte count and only with it");
+  const uint64_t ip = state_indiv_payload(c), lp = state_loc_payload(c);
+  const uint32_t K = c->cfg.k;
+  const uint64_t J = 2 * (uint64_t)K, arr = (uint64_t)c->cfg.l * J * sizeof(double);
+  // ---- validate everything first: nothing below this block fails for a reason the blobs carry
+  tsamd_state_pending pr;
+  memset(&pr, 0, sizeof pr);
+  if (indiv) {
+    if (int rc = state_check_header(c, "indiv", TSAMD_STATE_PART_INDIV, indiv, indiv_bytes, ip)) return rc;
+    const double *g = (const double *)((const uint8_t *)indiv + sizeof(tsamd_state_header));  // (128-byte header: as aligned as the blob)
+    const size_t nk = (size_t)c->n_local * K;
+    for (size_t i = 0; i < nk; ++i) {
+      double v;
+      memcpy(&v, g + i, sizeof v);
+      if (!(v >= 1e-8) || !std::isfinite(v)) return fail(c, TSAMD_EINVAL, "state import: gamma[%zu] must be finite and >= 1e-8", i);
+    }
+    for (size_t i = 0; i < nk; ++i) {
+      double v;
+      memcpy(&v, g + nk + i, sizeof v);
+      if (!(v >= 0.0) || !std::isfinite(v)) return fail(c, TSAMD_EINVAL, "state import: w[%zu] must be finite and >= 0", i);
+    }
+  }
+  if (loc) {
+    if (int rc = state_check_header(c, "loc", TSAMD_STATE_PART_LOC, loc, loc_bytes, lp)) return rc;
+    const uint8_t *pay = (const uint8_t *)loc + sizeof(tsamd_state_header);
+    const size_t nlj = (size_t)c->cfg.l * J;
+    for (size_t i = 0; i < 2 * nlj; ++i) {
+      double v;
+      memcpy(&v, pay + i * sizeof(double), sizeof v);
+      if (!(v > 0.0) || !std::isfinite(v)) return fail(c, TSAMD_EINVAL, "state import: %s[%zu] must be positive and finite", i < nlj ? "lambda" : "eb", i < nlj ? i : i - nlj);
+    }
+    const uint8_t *q = pay + 2 * arr;
+    memcpy(&pr, q, sizeof pr);
+    if (pr.valid > 1u || pr.hol > 1u || pr.done > 1u) return fail(c, TSAMD_EINVAL, "state import: pending record: valid, hol and done are 0 or 1");
+    // (loc and iters are read by the kernels whether or not the record is valid: a column address is formed from loc)
+    if (pr.loc >= c->cfg.l) return fail(c, TSAMD_EINVAL, "state import: pending record: loc = %u >= l = %u", pr.loc, c->cfg.l);
+    if (pr.iters > c->cfg.max_inner) return fail(c, TSAMD_EINVAL, "state import: pending record: iters = %u > max_inner = %u", pr.iters, c->cfg.max_inner);
+    if (pr.valid) {
+      if (!pr.done) return fail(c, TSAMD_EINVAL, "state import: pending record: done = 0 (an update in the middle of its passes cannot be restored)");
+      for (size_t j = 0; j < 2 * J; ++j) {
+        double v;
+        memcpy(&v, q + sizeof pr + j * sizeof(double), sizeof v);
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(c, TSAMD_EINVAL, "state import: pending record: %s[%zu] must be positive and finite", j < J ? "lam" : "eb", j < J ? j : j - J);
+      }
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->dev));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // ---- device allocations and the context's own live record before the first write
+  State st;
+  if (loc) {
+    HIP_TRY(c, hipMemcpyAsync(&st, &c->p.ctl->st[state_live_slot(c)], sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (indiv) {
+    if (int rc = ensure_state_stage(c, ip)) return rc;
+    const uint32_t TN = state_tile(K);
+    double *d_stage = c->d_state;
+    int rc = state_copy(c, (void *)((const uint8_t *)indiv + sizeof(tsamd_state_header)), d_stage, ip, false);
+    hipError_t e = hipSuccess;
+    if (rc == TSAMD_OK) {
+      hipLaunchKernelGGL(ts_state_unpack, dim3(c->npad / TN, 2), dim3(256), (size_t)K * (TN + 1) * sizeof(double), c->stream, c->p.gam, c->p.w,
+                         c->p.cnt, c->npad, K, c->n_local, TN, (const double *)d_stage);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, TSAMD_EHIP, "state import: %s", hipGetErrorString(e));
+  }
+  if (loc) {
+    const uint8_t *pay = (const uint8_t *)loc + sizeof(tsamd_state_header);
+    if (int rc = state_copy(c, (void *)pay, c->p.lam, arr, false)) return rc;
+    if (int rc = state_copy(c, (void *)(pay + arr), c->p.eb, arr, false)) return rc;
+    // the record goes into BOTH slots, so that the next call's first kernel finds it whatever its parity is; idx and the
+    // epoch (tags of the peer-to-peer exchange) stay the context's own
+    const uint8_t *q = pay + 2 * arr;
+    st.valid = pr.valid;
+    st.loc = pr.loc;
+    st.hol = pr.hol;
+    st.iters = pr.iters;
+    st.done = pr.done;
+    st.nrows = 0u;
+    memset(st.lam, 0, sizeof st.lam);
+    memset(st.eb, 0, sizeof st.eb);
+    memcpy(st.lam, q + sizeof pr, J * sizeof(double));
+    memcpy(st.eb, q + sizeof pr + J * sizeof(double), J * sizeof(double));
+    unsigned long long counters[1 + TSAMD_PASS_HIST_BINS];
+    memcpy(counters, q + sizeof pr + 2 * J * sizeof(double), sizeof counters);
+    HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->st[0], &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->st[1], &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->total_passes, counters, sizeof counters, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->last_iters, &pr.iters, sizeof pr.iters, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the sources are on this stack frame)
+    // the pinned mirrors the getters read (count_snp): inner passes of the last update, total passes, histogram
+    volatile unsigned long long *hw = c->h_error;
+    hw[1] = pr.iters;
+    for (int b = 0; b < 1 + TSAMD_PASS_HIST_BINS; ++b) hw[2 + b] = counters[b];
+    c->tail_step_pending = pr.valid != 0u && pr.hol == 0u;
+  }
   return TSAMD_OK;
 }
 

@@ -44,6 +44,111 @@ __global__ void ts_export_loc(const double *lam, uint32_t K, uint32_t first_loc,
   }
 }
 
+// ---------------------------------------------------------------------------
+// tsamd_state_export / tsamd_state_import: the engine's K-major padded arrays gam, w ([K][npad]) and c_n ([npad]) <-> the
+// individual part's payload in one device staging buffer: gamma[n_local][K], w[n_local][K] (row-major, unpadded), c_n[n_local].
+// A transpose through LDS, one tile of TN individuals x K values per workgroup and array (blockIdx.y: 0 gamma -- these
+// workgroups also move the tile's c_n --, 1 w): on the K-major side thread e takes the double2 at (row e / (TN/2), pair
+// e % (TN/2)) -- TN/2 consecutive 16-byte accesses per row, every row start a multiple of 16 bytes (TN and npad are
+// multiples of 32) --, on the row-major side the tile is ONE contiguous run of rows x K doubles, taken as double2 on even
+// GLOBAL element indices (the w section starts at element n_local * K, which may be odd) with at most one single double at
+// either end.  TN = state_tile(K) keeps a tile near 2048 values for any K in 1 .. 128 (LDS: K (TN + 1) doubles <= 33 KB,
+// passed as dynamic shared memory).  Independent workgroups, no atomics, no waiting of any kind; every access is bounded by
+// the tile's own row count.
+__host__ __device__ constexpr uint32_t state_tile(uint32_t K) { return K <= 8u ? 256u : K <= 16u ? 128u : K <= 32u ? 64u : 32u; }
+
+// this thread's share of the contiguous run [g0, g0 + cnt) of doubles at `base`, through fn(pointer, elements 1 or 2, index
+// of the first one within the run)
+template <typename F>
+__device__ __forceinline__ void state_run(uint64_t g0, uint32_t cnt, F fn) {
+  const uint32_t head = (uint32_t)(g0 & 1ull) < cnt ? (uint32_t)(g0 & 1ull) : cnt;  // a single double up to the first even index
+  const uint32_t pairs = (cnt - head) / 2u;
+  const uint32_t tail = cnt - head - 2u * pairs;
+  if (head && threadIdx.x == 0) fn(0u, 1u);
+  for (uint32_t e = threadIdx.x; e < pairs; e += blockDim.x) fn(head + 2u * e, 2u);
+  if (tail && threadIdx.x == blockDim.x - 1u) fn(cnt - 1u, 1u);
+}
+
+// grid (ceil(n_local / TN), 2): gam / w / c_n -> staging
+__global__ __launch_bounds__(256) void ts_state_pack(const double *gam, const double *w, const uint32_t *cnt, uint32_t npad,
+                                                     uint32_t K, uint32_t n_local, uint32_t TN, double *stage) {
+  extern __shared__ double s_tile[];  // [K][TN + 1]
+  const uint32_t n0 = blockIdx.x * TN;
+  if (n0 >= n_local) return;
+  const uint32_t rows = min(TN, n_local - n0);
+  const double *src = blockIdx.y ? w : gam;
+  const uint32_t half = TN / 2u, ld = TN + 1u;
+  for (uint32_t e = threadIdx.x; e < K * half; e += blockDim.x) {  // (n0 + TN <= npad: TN divides npad)
+    const uint32_t k = e / half, pr = e % half;
+    const double2 v = reinterpret_cast<const double2 *>(src + (size_t)k * npad + n0)[pr];
+    s_tile[k * ld + 2u * pr] = v.x;
+    s_tile[k * ld + 2u * pr + 1u] = v.y;
+  }
+  __syncthreads();
+  const uint64_t g0 = (uint64_t)blockIdx.y * n_local * K + (uint64_t)n0 * K;
+  state_run(g0, rows * K, [&](uint32_t f, uint32_t cntf) {
+    const double a = s_tile[(f % K) * ld + f / K];
+    if (cntf == 2u) {
+      const double b = s_tile[((f + 1u) % K) * ld + (f + 1u) / K];
+      *reinterpret_cast<double2 *>(stage + g0 + f) = make_double2(a, b);
+    } else {
+      stage[g0 + f] = a;
+    }
+  });
+  if (blockIdx.y == 0u) {  // c_n of the tile: uint4 while four individuals are left (both sides 16-byte aligned: n0 is a multiple of 32)
+    uint32_t *dst = reinterpret_cast<uint32_t *>(stage + (size_t)2 * n_local * K) + n0;
+    for (uint32_t q = threadIdx.x; q < (rows + 3u) / 4u; q += blockDim.x) {
+      if (4u * q + 4u <= rows)
+        reinterpret_cast<uint4 *>(dst)[q] = reinterpret_cast<const uint4 *>(cnt + n0)[q];
+      else
+        for (uint32_t i = 4u * q; i < rows; ++i) dst[i] = cnt[n0 + i];
+    }
+  }
+}
+
+// grid (npad / TN, 2): staging -> gam / w / c_n; the padding individuals [n_local, npad) get what tsamd_create gives them
+// (gamma = w = 1, c_n = 0)
+__global__ __launch_bounds__(256) void ts_state_unpack(double *gam, double *w, uint32_t *cnt, uint32_t npad, uint32_t K,
+                                                       uint32_t n_local, uint32_t TN, const double *stage) {
+  extern __shared__ double s_tile[];  // [K][TN + 1]
+  const uint32_t n0 = blockIdx.x * TN;
+  if (n0 >= npad) return;
+  const uint32_t rows = n0 < n_local ? min(TN, n_local - n0) : 0u;
+  double *dstk = blockIdx.y ? w : gam;
+  const uint32_t half = TN / 2u, ld = TN + 1u;
+  const uint64_t g0 = (uint64_t)blockIdx.y * n_local * K + (uint64_t)n0 * K;
+  state_run(g0, rows * K, [&](uint32_t f, uint32_t cntf) {
+    if (cntf == 2u) {
+      const double2 v = *reinterpret_cast<const double2 *>(stage + g0 + f);
+      s_tile[(f % K) * ld + f / K] = v.x;
+      s_tile[((f + 1u) % K) * ld + (f + 1u) / K] = v.y;
+    } else {
+      s_tile[(f % K) * ld + f / K] = stage[g0 + f];
+    }
+  });
+  __syncthreads();
+  for (uint32_t e = threadIdx.x; e < K * half; e += blockDim.x) {
+    const uint32_t k = e / half, pr = e % half;
+    const double a = 2u * pr < rows ? s_tile[k * ld + 2u * pr] : 1.0;
+    const double b = 2u * pr + 1u < rows ? s_tile[k * ld + 2u * pr + 1u] : 1.0;
+    reinterpret_cast<double2 *>(dstk + (size_t)k * npad + n0)[pr] = make_double2(a, b);
+  }
+  if (blockIdx.y == 0u) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(stage + (size_t)2 * n_local * K) + n0;
+    for (uint32_t q = threadIdx.x; q < TN / 4u; q += blockDim.x) {
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (4u * q + 4u <= rows) {
+        v = reinterpret_cast<const uint4 *>(src)[q];
+      } else {
+        if (4u * q < rows) v.x = src[4u * q];
+        if (4u * q + 1u < rows) v.y = src[4u * q + 1u];
+        if (4u * q + 2u < rows) v.z = src[4u * q + 2u];
+      }
+      reinterpret_cast<uint4 *>(cnt + n0)[q] = v;
+    }
+  }
+}
+
 // after a direct (unstaged) upload of columns [first_loc, first_loc + n_locs): the individuals past
 // the shard's end that share its last byte (neighbours' bits, or PLINK's zero padding) -> missing
 __global__ void ts_fix_tail(uint8_t *bed, uint64_t colstride, uint32_t first_loc, uint32_t n_locs, uint64_t last_byte,

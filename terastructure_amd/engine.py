@@ -230,6 +230,32 @@ class Engine:
                                               C.byref(s), C.byref(c)))
         return s.value, c.value, sums, cnts
 
+    # -- the full state: save / restore ------------------------------------------
+    def state_sizes(self):
+        """(indiv_bytes, loc_bytes) of the two state blobs -- tsamd_state_sizes"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.h.tsamd_state_sizes(self.ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def state_export(self, indiv=True, loc=True):
+        """(indiv, loc): the shard's own part (gamma, the stored w, c_n) and the location part (lambda, the stored
+        exp(Elogbeta), the pending gamma step, the pass counters) as uint8 arrays -- tsamd_state_export; a part that is
+        not asked for comes back as None"""
+        ni, nl = self.state_sizes()
+        a = np.empty(ni, dtype=np.uint8) if indiv else None
+        b = np.empty(nl, dtype=np.uint8) if loc else None
+        self._check(self.h.tsamd_state_export(self.ctx, a.ctypes.data if indiv else None, ni if indiv else 0,
+                                              b.ctypes.data if loc else None, nl if loc else 0))
+        return a, b
+
+    def state_import(self, indiv=None, loc=None):
+        """restore either part or both (uint8 arrays / bytes from state_export); validated before anything is touched --
+        tsamd_state_import"""
+        a = None if indiv is None else np.ascontiguousarray(np.frombuffer(indiv, dtype=np.uint8))
+        b = None if loc is None else np.ascontiguousarray(np.frombuffer(loc, dtype=np.uint8))
+        self._check(self.h.tsamd_state_import(self.ctx, None if a is None else a.ctypes.data, 0 if a is None else a.size,
+                                              None if b is None else b.ctypes.data, 0 if b is None else b.size))
+
     # -- multi-GPU --------------------------------------------------------------
     def comm_unique_id(self):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES)()
