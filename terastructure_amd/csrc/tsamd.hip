@@ -23,6 +23,8 @@
 #include "tsamd_holblock_kernels.h"
 #include "tsamd_hybrid_kernels.h"
 #include "tsamd_wide_kernels.h"
+#include "tsamd_plan.h"
+#include "tsamd_unit.h"
 
 using namespace tsamd;
 
@@ -90,8 +92,8 @@ struct tsamd_ctx {
   int dev = 0;
   hipStream_t stream = nullptr;
   uint32_t n_begin = 0, n_local = 0, npad = 0;
-  bool wide = false;  // K above TSAMD_SPECIALIZED_K: run-time-K fallback kernels (tsamd_wide_kernels.h)
-  uint32_t grid = 0, block = 256, grid_first = 0, first_vec = 1;  // plain-pass and first-pass launch geometry
+  PlanInputs in;    // the facts the launch plan is computed from (device, occupancy answers, environment; the exchange in force) ...
+  LaunchPlan plan;  // ... and the plan: kernel family, launch mode and geometries (plan_launch, tsamd_plan.h; replaced as a whole by replan())
   DevParams p{};
   uint32_t *d_sched = nullptr;
   uint32_t sched_cap = 0;
@@ -117,20 +119,9 @@ struct tsamd_ctx {
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
-  bool p2p = false;
-  bool split = false;  // lambda_t leaves the pass via ctl->lt and the epilogue is its own kernel
   bool rccl_graph = false;  // TSAMD_RCCL_GRAPH=1: capture the RCCL all-reduce into the replayed graphs
-  bool resident = false;    // plain passes of a SNP run as ONE launch (ts_resident) instead of max_inner - 1
-  bool persistent = false;  // ... and a whole schedule runs as ONE launch (ts_schedule: the weights never leave the registers)
-  bool can_resident = false, can_persistent = false;  // what the context qualifies for (tsamd_set_launch_mode)
-  bool hybrid = false;             // the whole-schedule kernel of this context is ts_hybrid: the shard exceeds ts_schedule's register capacity
-  bool can_holblock = false;       // ... and validation-mode schedules run batched (ts_holblock) while it runs ts_schedule
-  bool can_hybhol = false;         // ... or (one GPU) batched by ts_hybhol while it runs ts_hybrid
   bool tail_step_pending = false;  // the last entry enqueued was a training update: its gamma step is pending
   uint64_t holblock_launches = 0, holblock_locs = 0;
-  uint32_t sched_grid = 0, sched_chunk = 0;  // launch geometry of ts_schedule (= the plain pass' on one GPU; its own when sharded)
-  uint32_t res_grid = 0, res_chunk = 0;      // ... and of ts_resident: the same shard, shrunk only as far as ITS exchange has one level
-  uint32_t device_share = 1;  // contexts whose resident kernels share this device (tests: several ranks on one GPU)
   ResXchg *res = nullptr;   // their in-launch exchange buffer
   unsigned long long *h_error = nullptr;  // pinned: tag of a bounded in-kernel wait that gave up (0: none)
   // profiling
@@ -194,20 +185,8 @@ int fail(tsamd_ctx *ctx, int code, const char *fmt, ...) {
 #define CHECK_CTX(ctx) \
   if (!(ctx)) return TSAMD_EINVAL
 
-// launchers of the K-specialised kernels, one per translation unit (tsamd_inst.hip)
-#define TSAMD_DECL(k)                                                                                        \
-  void launch_k##k(int, uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, uint32_t, uint32_t); \
-  int first_blocks_per_cu_k##k(int);                                                                         \
-  int resident_blocks_per_cu_k##k();                                                                         \
-  void launch_schedule_k##k(uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, const uint32_t *, uint32_t, uint32_t); \
-  int schedule_blocks_per_cu_k##k();                                                                         \
-  void launch_holblock_k##k(uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, const uint32_t *, uint32_t, uint32_t); \
-  int holblock_blocks_per_cu_k##k();                                                                         \
-  void launch_hybrid_k##k(uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, const uint32_t *, uint32_t, uint32_t); \
-  int hybrid_blocks_per_cu_k##k();                                                                           \
-  void launch_hybhol_k##k(uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, const uint32_t *, uint32_t, uint32_t); \
-  int hybhol_blocks_per_cu_k##k();                                                                           \
-  int hybhol_batch_k##k();
+// the K-specialised kernels, one ops object per translation unit (tsamd_unit.h)
+#define TSAMD_DECL(k) extern const PassOps pass_ops_k##k; extern const WholeOps schedule_ops_k##k, holblock_ops_k##k, hybrid_ops_k##k, hybhol_ops_k##k;
 #define TSAMD_ALL_K(X)                                                                             \
   X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17)     \
   X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
@@ -216,32 +195,18 @@ namespace tsamd {
 TSAMD_ALL_K(TSAMD_DECL)  // tsamd_inst.hip, tsamd_sched.hip, tsamd_hol.hip, tsamd_hyb.hip and tsamd_hhol.hip: five translation units per K
 }
 namespace {
-#define TSAMD_ENTRY(k) tsamd::launch_k##k,
-const LaunchFn kLaunchers[TSAMD_SPECIALIZED_K + 1] = {nullptr, TSAMD_ALL_K(TSAMD_ENTRY)};
-#define TSAMD_OCC_ENTRY(k) tsamd::first_blocks_per_cu_k##k,
-int (*const kFirstBlocksPerCu[TSAMD_SPECIALIZED_K + 1])(int) = {nullptr, TSAMD_ALL_K(TSAMD_OCC_ENTRY)};
-#define TSAMD_RES_ENTRY(k) tsamd::resident_blocks_per_cu_k##k,
-int (*const kResidentBlocksPerCu[TSAMD_SPECIALIZED_K + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_RES_ENTRY)};
 static_assert(kResidentMaxK == TSAMD_SPECIALIZED_K, "TSAMD_ALL_K lists K = 1 .. kResidentMaxK");
-typedef void (*ScheduleFn)(uint32_t, uint32_t, hipStream_t, const DevParams &, uint32_t, const uint32_t *, uint32_t, uint32_t);
-#define TSAMD_SCHED_ENTRY(k) tsamd::launch_schedule_k##k,
-const ScheduleFn kScheduleLaunchers[kResidentMaxK + 1] = {nullptr, TSAMD_ALL_K(TSAMD_SCHED_ENTRY)};
-#define TSAMD_SCHED_OCC_ENTRY(k) tsamd::schedule_blocks_per_cu_k##k,
-int (*const kScheduleBlocksPerCu[kResidentMaxK + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_SCHED_OCC_ENTRY)};
-#define TSAMD_HOL_ENTRY(k) tsamd::launch_holblock_k##k,
-const ScheduleFn kHolblockLaunchers[kResidentMaxK + 1] = {nullptr, TSAMD_ALL_K(TSAMD_HOL_ENTRY)};
-#define TSAMD_HOL_OCC_ENTRY(k) tsamd::holblock_blocks_per_cu_k##k,
-int (*const kHolblockBlocksPerCu[kResidentMaxK + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_HOL_OCC_ENTRY)};
-#define TSAMD_HYB_ENTRY(k) tsamd::launch_hybrid_k##k,
-const ScheduleFn kHybridLaunchers[kResidentMaxK + 1] = {nullptr, TSAMD_ALL_K(TSAMD_HYB_ENTRY)};
-#define TSAMD_HYB_OCC_ENTRY(k) tsamd::hybrid_blocks_per_cu_k##k,
-int (*const kHybridBlocksPerCu[kResidentMaxK + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_HYB_OCC_ENTRY)};
-#define TSAMD_HHOL_ENTRY(k) tsamd::launch_hybhol_k##k,
-const ScheduleFn kHybholLaunchers[kResidentMaxK + 1] = {nullptr, TSAMD_ALL_K(TSAMD_HHOL_ENTRY)};
-#define TSAMD_HHOL_OCC_ENTRY(k) tsamd::hybhol_blocks_per_cu_k##k,
-int (*const kHybholBlocksPerCu[kResidentMaxK + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_HHOL_OCC_ENTRY)};
-#define TSAMD_HHOL_BATCH_ENTRY(k) tsamd::hybhol_batch_k##k,
-int (*const kHybholBatch[kResidentMaxK + 1])() = {nullptr, TSAMD_ALL_K(TSAMD_HHOL_BATCH_ENTRY)};
+#define TSAMD_PASS_ENTRY(k) &tsamd::pass_ops_k##k,
+const PassOps *const kPass[TSAMD_SPECIALIZED_K + 1] = {nullptr, TSAMD_ALL_K(TSAMD_PASS_ENTRY)};
+#define TSAMD_SCHED_ENTRY(k) &tsamd::schedule_ops_k##k,
+#define TSAMD_HOL_ENTRY(k) &tsamd::holblock_ops_k##k,
+#define TSAMD_HYB_ENTRY(k) &tsamd::hybrid_ops_k##k,
+#define TSAMD_HHOL_ENTRY(k) &tsamd::hybhol_ops_k##k,
+const WholeOps *const kWhole[kFamilies][kResidentMaxK + 1] = {  // [Family][K]
+    {nullptr, TSAMD_ALL_K(TSAMD_SCHED_ENTRY)},
+    {nullptr, TSAMD_ALL_K(TSAMD_HOL_ENTRY)},
+    {nullptr, TSAMD_ALL_K(TSAMD_HYB_ENTRY)},
+    {nullptr, TSAMD_ALL_K(TSAMD_HHOL_ENTRY)}};
 
 __global__ void ts_fill_f64(double *p, size_t n, double v0, double v1) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -250,6 +215,8 @@ __global__ void ts_fill_f64(double *p, size_t n, double v0, double v1) {
 
 // Every kernel of the state-machine sequence gets the next parity bit (tsamd_device.h).
 uint32_t next_parity(tsamd_ctx *c) { return (uint32_t)(c->q++ & 1u); }
+
+bool p2p(const tsamd_ctx *c) { return c->in.exchange == Exchange::kP2p; }
 
 // one pass = ts_pass [+ ts_reduce_rows + all-reduce when sharded]; `pass` = its index within
 // the SNP (0 = first pass).  Odd plain passes sweep backwards (bit 1 of the parity argument).
@@ -260,18 +227,19 @@ int enqueue_pass(tsamd_ctx *c, uint32_t pass) {
   // rows of the previous launch of the sequence: a first pass follows a plain pass (or a
   // kernel that left nothing pending), a plain pass follows the first pass or a plain pass
   const uint32_t hint = c->prev_rows;
-  if (c->wide) {
+  const LaunchPlan &pl = c->plan;
+  if (pl.wide) {
     if (first)
-      hipLaunchKernelGGL((ts_pass_wide<true>), dim3(c->grid_first), dim3(kWideBlock), 0, c->stream, c->p, par_arg, hint);
+      hipLaunchKernelGGL((ts_pass_wide<true>), dim3(pl.grid_first), dim3(kWideBlock), 0, c->stream, c->p, par_arg, hint);
     else
-      hipLaunchKernelGGL((ts_pass_wide<false>), dim3(c->grid_first), dim3(kWideBlock), 0, c->stream, c->p, par_arg, hint);
-    c->prev_rows = c->grid_first;
+      hipLaunchKernelGGL((ts_pass_wide<false>), dim3(pl.grid_first), dim3(kWideBlock), 0, c->stream, c->p, par_arg, hint);
+    c->prev_rows = pl.grid_first;
   } else if (first)
-    kLaunchers[c->cfg.k](kLaunchFirst, c->grid_first, c->first_vec == 2 ? 1u : 0u, c->stream, c->p, par_arg, hint, 0u);
+    kPass[c->cfg.k]->launch(kLaunchFirst, pl.grid_first, pl.first_vec == 2 ? 1u : 0u, c->stream, c->p, par_arg, hint, 0u);
   else
-    kLaunchers[c->cfg.k](kLaunchPass, c->grid, c->block, c->stream, c->p, par_arg, hint, 0u);
-  if (!c->wide) c->prev_rows = first ? c->grid_first : c->grid;
-  if (c->split && !c->p2p) {  // (peer-to-peer: every workgroup has already pushed its row to every rank)
+    kPass[c->cfg.k]->launch(kLaunchPass, pl.grid, pl.block, c->stream, c->p, par_arg, hint, 0u);
+  if (!pl.wide) c->prev_rows = first ? pl.grid_first : pl.grid;
+  if (pl.split && !p2p(c)) {  // (peer-to-peer: every workgroup has already pushed its row to every rank)
     hipLaunchKernelGGL(ts_reduce_rows, dim3(1), dim3(256), 0, c->stream, c->p, par);
     Ctl *ctl = c->p.ctl;
     if (c->comm) {
@@ -292,7 +260,7 @@ void enqueue_begin(tsamd_ctx *c, uint32_t n, bool drop_pending, const uint32_t *
 }
 
 void enqueue_flush(tsamd_ctx *c) {
-  if (c->wide)
+  if (c->plan.wide)
     hipLaunchKernelGGL((ts_flush<kWideBlock>), dim3(1), dim3(kWideBlock), 0, c->stream, c->p, next_parity(c));
   else  // 256 = workgroup size of ts_pass<K, true, ...>
     hipLaunchKernelGGL((ts_flush<256>), dim3(1), dim3(256), 0, c->stream, c->p, next_parity(c));
@@ -311,7 +279,8 @@ int prof_event(tsamd_ctx *c, std::vector<hipEvent_t> &evs, uint32_t slot, hipEve
   return TSAMD_OK;
 }
 
-int enqueue_snp(tsamd_ctx *c) {
+// resident: every plain pass of the SNP in one launch (TSAMD_LAUNCH_PER_SNP)
+int enqueue_snp(tsamd_ctx *c, bool resident) {
   const bool prof = c->prof && c->n_ev_first < kProfCap;
   if (c->prof && !prof) c->prof_capped = true;
   hipEvent_t e = nullptr;
@@ -329,11 +298,11 @@ int enqueue_snp(tsamd_ctx *c) {
       HIP_TRY(c, hipEventRecord(e, c->stream));
     }
   }
-  if (c->resident) {  // every plain pass of the SNP in one launch
+  if (resident) {
     if (rc == TSAMD_OK) {
       const uint32_t par = next_parity(c);
-      kLaunchers[c->cfg.k](kLaunchResident, c->res_grid, c->res_chunk, c->stream, c->p, par, c->prev_rows, c->launch_serial++);
-      c->prev_rows = c->res_grid;
+      kPass[c->cfg.k]->launch(kLaunchResident, c->plan.snp.grid, c->plan.snp.chunk, c->stream, c->p, par, c->prev_rows, c->launch_serial++);
+      c->prev_rows = c->plan.snp.grid;
     }
   } else {
     for (uint32_t i = 1; rc == TSAMD_OK && i < c->cfg.max_inner; ++i) rc = enqueue_pass(c, i);
@@ -357,8 +326,6 @@ void destroy_graph(tsamd_ctx *c) {
   c->graphs_ready = false;
 }
 
-// kernels of the state-machine sequence per SNP (ts_reduce_rows shares its pass' parity)
-uint32_t kernels_per_snp(const tsamd_ctx *c) { return c->resident ? 2u : c->cfg.max_inner; }
 // SNPs per ts_schedule launch at most (a launch of this many runs for seconds; every in-kernel wait is bounded)
 constexpr uint32_t kScheduleChunk = 1u << 16;
 
@@ -371,10 +338,10 @@ int build_graph(tsamd_ctx *c, uint32_t level, uint32_t par0) {
   const uint32_t rows_save = c->prev_rows;
   c->q = par0;
   // in replay the first kernel follows the last kernel of a SNP sequence (or nothing pending)
-  c->prev_rows = c->cfg.max_inner > 1 ? c->grid : c->grid_first;
+  c->prev_rows = c->cfg.max_inner > 1 ? c->plan.grid : c->plan.grid_first;
   HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = TSAMD_OK;
-  for (uint32_t s = 0; s < (1u << level) && rc == TSAMD_OK; ++s) rc = enqueue_snp(c);
+  for (uint32_t s = 0; s < (1u << level) && rc == TSAMD_OK; ++s) rc = enqueue_snp(c, false);  // (graphs_allowed: launch per pass only)
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(c->stream, &g);
   c->q = q_save;
@@ -402,19 +369,19 @@ int build_all_graphs(tsamd_ctx *c) {
   return TSAMD_OK;
 }
 
-bool graphs_allowed(const tsamd_ctx *c) {
+bool graphs_allowed(const tsamd_ctx *c, int mode) {
   // (RCCL all-reduce inside the captured sequence: opt-in, TSAMD_RCCL_GRAPH=1 on every rank)
-  const bool comm_graph = c->comm && !c->p2p && c->rccl_graph;
+  const bool comm_graph = c->comm && !p2p(c) && c->rccl_graph;
   // (resident plain passes: two launches per SNP of ~50 us each -- eager launches stay far ahead of the
   // device and have neither the submission cost of a graph nor the ~8 us boundary between graphs)
-  return !(c->cfg.flags & TSAMD_FLAG_NO_GRAPH) && (!c->comm || c->p2p || comm_graph) && !c->prof && !c->resident;
+  return !(c->cfg.flags & TSAMD_FLAG_NO_GRAPH) && (!c->comm || p2p(c) || comm_graph) && !c->prof && mode == TSAMD_LAUNCH_PER_PASS;
 }
 
 // the graphs are built on first use; with an RCCL all-reduce inside, the first collective runs
 // outside the capture (RCCL sets its channels up lazily)
 int ensure_graphs(tsamd_ctx *c) {
   if (c->graphs_ready) return TSAMD_OK;
-  if (c->comm && !c->p2p && c->rccl_graph) {
+  if (c->comm && !p2p(c) && c->rccl_graph) {
     ncclResult_t r = g_rccl.AllReduce(c->p.ctl->lt[0], c->p.ctl->lt_sum[0], 2 * c->cfg.k, ncclDouble, ncclSum, c->comm,
                                       c->stream);
     if (r != ncclSuccess) return fail(c, TSAMD_ECOMM, "ncclAllReduce: %s", g_rccl.GetErrorString(r));
@@ -428,98 +395,34 @@ uint32_t env_u32(const char *name, uint32_t dflt) {
   return (s && *s) ? (uint32_t)std::max(0, atoi(s)) : dflt;
 }
 
-// Launch geometry.  The pass kernel is a streaming reduction: enough waves per CU to cover
-// HBM latency, but few workgroups, because every workgroup of the NEXT launch adds all
-// partial rows up again (and, sharded peer-to-peer, every workgroup sends its row to every
-// rank: max_grid = kXchgBlocks there).
-void configure_launch(tsamd_ctx *c, uint32_t max_grid) {
-  DevParams &p = c->p;
-  if (c->wide) {  // one individual per thread, at most kWideItems individuals per thread
-    uint32_t chunk = (p.npad + max_grid - 1) / max_grid;
-    chunk = (chunk + kWideBlock - 1) / kWideBlock * kWideBlock;
-    p.chunk_first = p.chunk = chunk;
-    c->grid_first = c->grid = (p.npad + chunk - 1) / chunk;
-    c->block = kWideBlock;
-    return;
-  }
-  uint32_t block = env_u32("TSAMD_BLOCK", (c->cfg.k <= 16 && p.npairs >= 256u * 1024u) ? 512 : 256);
-  if (block != 256u && block != 512u && block != 1024u) block = 256u;
-  if (block == 1024u && c->cfg.k > 8) block = 512u;  // register budget of the pipelined loop
-  auto geometry = [&](uint32_t nitems, uint32_t blk, uint32_t target, uint32_t &chunk, uint32_t &grid) {
-    target = std::min<uint32_t>(std::max<uint32_t>(target, 1u), max_grid);
-    chunk = (nitems + target - 1) / target;
-    chunk = (chunk + blk - 1) / blk * blk;
-    grid = (nitems + chunk - 1) / chunk;
-  };
-  c->block = block;
-  c->first_vec = env_u32("TSAMD_FIRST_VEC", 1) == 2 ? 2 : 1;
-  // Ranks that SHARE one device (tests, rehearsals: TSAMD_DEVICE_SHARE=<ranks>): a pass kernel of the peer-to-peer sequence
-  // spins in its prologue until every rank's rows of the previous pass have arrived, so all ranks' kernels must fit the
-  // device together -- a first pass that fills every compute unit (it is register-bound: one workgroup per unit from K = 12
-  // on) would keep its peers' previous passes off the device until its bounded wait gives up (4 ranks x 250 000 individuals,
-  // K = 20: "timed out waiting for a peer (epoch 2)").  Each rank gets its share of the workgroups.  One rank per device: 1.
-  const uint32_t share = std::max<uint32_t>(1u, c->device_share);
-  geometry(p.npairs, block, env_u32("TSAMD_GRID", share > 1u ? std::max<uint32_t>(8u, 256u / share) : 256u), p.chunk, c->grid);
-  // first pass: exactly as many workgroups as are resident at once (one round; the kernel is
-  // register-bound, so that is 2 per compute unit at K = 8 and 1 from K = 12 on)
-  uint32_t first_target = 512;
-  {
-    hipDeviceProp_t prop;
-    const int nb = kFirstBlocksPerCu[c->cfg.k]((int)c->first_vec);
-    if (nb > 0 && hipGetDeviceProperties(&prop, c->dev) == hipSuccess && prop.multiProcessorCount > 0)
-      first_target = (uint32_t)prop.multiProcessorCount * (uint32_t)std::min(nb, 4);
-  }
-  if (share > 1u) first_target = std::max<uint32_t>(8u, std::min<uint32_t>(first_target, 256u) / share);
-  geometry(p.npad / c->first_vec, 256, env_u32("TSAMD_GRID_FIRST", first_target), p.chunk_first, c->grid_first);
+// The environment variables that shape the launch plan, read here and nowhere else: at context creation, when an exchange
+// is activated and for the geometry of a recovery.  (TSAMD_HOLBLOCK and TSAMD_SINGLE_ROUTE are read per call.)
+Knobs read_knobs() {
+  Knobs kn;
+  kn.block = env_u32("TSAMD_BLOCK", kKnobUnset);
+  kn.grid = env_u32("TSAMD_GRID", kKnobUnset);
+  kn.grid_first = env_u32("TSAMD_GRID_FIRST", kKnobUnset);
+  kn.first_vec = env_u32("TSAMD_FIRST_VEC", 1);
+  kn.resident = env_u32("TSAMD_RESIDENT", 1);
+  kn.persistent = env_u32("TSAMD_PERSISTENT", 1);
+  kn.hybrid = env_u32("TSAMD_HYBRID", 1);
+  kn.sched_workgroups = env_u32("TSAMD_SCHED_WORKGROUPS", 0);
+  kn.test_max_workgroups = env_u32("TSAMD_TEST_MAX_WORKGROUPS", 0);
+  return kn;
 }
 
-// Launch geometry of the resident kernels for a shard of `npad` padded individuals on at most `cap` workgroups (all
-// resident at once): items of resident_vec(K) individuals, a whole number of 256-thread rounds per workgroup.  False
-// when the shard does not fit resident_items(K) items per thread.
-// one_level: up to this many workgroups the kernel that will run exchanges in ONE level (ts_schedule: kResOneLevelGrid;
-// ts_resident: 16 at K <= 8, never above -- its sweep's registers leave no room for the wider form).
-bool resident_geometry(uint32_t k, uint32_t npad, uint32_t cap, uint32_t *grid, uint32_t *chunk, bool one_gpu = false,
-                       uint32_t one_level = (uint32_t)kResOneLevelGrid) {
-  if (cap == 0u || (int)k > kResidentMaxK) return false;
-  const uint32_t nitems = npad / (uint32_t)resident_vec((int)k);
-  auto rounds = [&](uint32_t workgroups) {
-    const uint32_t ch = (nitems + workgroups - 1u) / workgroups;
-    return (ch + (uint32_t)kResidentBlock - 1u) / (uint32_t)kResidentBlock;
-  };
-  uint32_t r = rounds(cap);
-  // (a sharded launch -- one_gpu false -- holds sharded_items(K) items per thread: one fewer than resident_items(K) at K = 14 and 16)
-  if (r > (uint32_t)(one_gpu ? resident_items((int)k) : sharded_items((int)k))) return false;
-  // Small shards on one GPU: up to kResOneLevelGrid workgroups exchange in ONE level (1.9 us against 3.0 per pass), which is
-  // worth a few more individuals per thread -- each costs about 0.33 K us per update (gamma step + ten sweeps), the nine
-  // shorter exchanges save about 10 (profiles/r03_experiments.md)
-  if (one_gpu && one_level > 0u && (nitems + r * (uint32_t)kResidentBlock - 1u) / (r * (uint32_t)kResidentBlock) > one_level) {
-    const uint32_t r1 = rounds(one_level);
-    if (r1 <= (uint32_t)resident_items((int)k) && (r1 - r) * k < 20u) r = r1;  // (measured with a threshold of 16: K = 8, N = 10 000: 39.0 against 43.7 us per update; K = 20, N = 8 000 would lose)
-  }
-  // ... and the smallest cohorts on ONE workgroup, which exchanges nothing at all (a pass is then a sweep, a fold and an
-  // epilogue: about 1 us), when its extra individuals per thread cost less than the exchanges they replace
-  if (one_gpu) {
-    const uint32_t r0 = rounds(1u);
-    if (r0 <= (uint32_t)resident_items((int)k) && (r0 - r) * k < 50u) r = r0;
-  }
-  *chunk = r * (uint32_t)kResidentBlock;
-  *grid = (nitems + *chunk - 1u) / *chunk;
-  return true;
-}
-
-// Launch geometry of ts_hybrid for a shard above ts_schedule's capacity: all `cap` workgroups, a whole number of 256-thread
-// rounds each; the first hy_reg_items(K) + hy_lds_items(K) rounds of a workgroup stay on chip, the rest is streamed.
-bool hybrid_geometry(uint32_t k, uint32_t npad, uint32_t cap, uint32_t *grid, uint32_t *chunk) {
-  if (cap == 0u || (int)k > kResidentMaxK) return false;
-  // (the kernel is bound by memory: ALL `cap` workgroups take an equal share -- a multiple of 16 individuals, i.e. of a column
-  // word and of 128 bytes of a weight row -- rather than whole 256-thread rounds on fewer workgroups; a workgroup's last round
-  // is then partly filled)
-  const uint32_t ch = ((npad + cap - 1u) / cap + 15u) / 16u * 16u;
-  const uint32_t r = (ch + (uint32_t)kResidentBlock - 1u) / (uint32_t)kResidentBlock;
-  if (r > (uint32_t)(hy_reg_items((int)k) + hy_lds_items((int)k) + kHybridMaxStreamed)) return false;
-  *chunk = ch;
-  *grid = (npad + ch - 1u) / ch;
-  return true;
+// what the kernels of this K answer about their register / LDS budget
+Occupancy probe_occupancy(uint32_t k) {
+  Occupancy o;
+  if (k > (uint32_t)TSAMD_SPECIALIZED_K) return o;
+  o.first[0] = kPass[k]->first_blocks_per_cu(1);
+  o.first[1] = kPass[k]->first_blocks_per_cu(2);
+  o.resident = kPass[k]->resident_blocks_per_cu();
+  o.schedule = kWhole[kFamSchedule][k]->blocks_per_cu();
+  o.holblock = kWhole[kFamHolblock][k]->blocks_per_cu();
+  o.hybrid = kWhole[kFamHybrid][k]->blocks_per_cu();
+  o.hybhol = kWhole[kFamHybhol][k]->blocks_per_cu();
+  return o;
 }
 
 bool alloc_res(tsamd_ctx *c) {
@@ -530,60 +433,25 @@ bool alloc_res(tsamd_ctx *c) {
   return true;
 }
 
-// ts_schedule on a shard: one launch per rank and schedule, weights resident, level 2 of the in-launch exchange across
-// the ranks (Xchg::res_sums).  Every rank must reach the same verdict, so it depends only on the configuration: up to 8
-// ranks, the reference's default learning-rate exponent, every rank's shard fits the register file of at most
-// min(256, CUs / device_share) workgroups and fills at least 8 of them (all 8 groups of every rank then post a sum).
-void choose_sharded_schedule(tsamd_ctx *c) {
-  const tsamd_config &cfg = c->cfg;
-  if (c->wide || cfg.world > 8u || (int)cfg.k > kResidentMaxK || cfg.nodekappa != 0.5 || cfg.max_inner < 2u || cfg.max_inner > 200u ||
-      env_u32("TSAMD_RESIDENT", 1) == 0u || env_u32("TSAMD_PERSISTENT", 1) == 0u || kScheduleBlocksPerCu[cfg.k]() < 1)
-    return;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, c->dev) != hipSuccess || prop.multiProcessorCount <= 0) return;
-  // (ranks sharing a device: the dispatcher deals a launch's workgroups round robin over the 8 XCDs, every rank's launch starting at the
-  // same one, so a rank may take floor(compute units per XCD / ranks) per XCD -- 3 ranks: 80 workgroups each, not 256 / 3 = 85, which put 33
-  // workgroups on five XCDs of 32 compute units and lost the launch to the co-residency check: every 3-rank ts_hybrid test of round 5 in fact ran
-  // its replay.  One rank per device: all compute units.)
-  const uint32_t per_xcd = (uint32_t)prop.multiProcessorCount / (uint32_t)kResGroups;
-  uint32_t cap = std::min<uint32_t>((uint32_t)(kResGroups * kResMembers),
-                                    c->device_share > 1u ? (uint32_t)kResGroups * (per_xcd / c->device_share) : (uint32_t)prop.multiProcessorCount);
-  if (env_u32("TSAMD_SCHED_WORKGROUPS", 0) >= (uint32_t)kResGroups) cap = std::min<uint32_t>(cap, env_u32("TSAMD_SCHED_WORKGROUPS", 0));  // (tuning knob, see tsamd_create)
-  if (cap < (uint32_t)kResGroups) return;
-  uint32_t my_grid = 0, my_chunk = 0;
-  bool hybrid = false;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    // first ts_schedule on every rank; if a rank's shard exceeds its register capacity, ts_hybrid on every rank (up to 4 ranks:
-    // the instantiations tsamd_hyb.hip carries)
-    hybrid = attempt == 1;
-    if (hybrid && (cfg.world > 4u || env_u32("TSAMD_HYBRID", 1) == 0u || kHybridBlocksPerCu[cfg.k]() < 1)) return;
-    bool ok = true, too_big = false;
-    for (uint32_t r = 0; r < cfg.world && ok; ++r) {
-      uint32_t b = 0, cnt = 0, grid = 0, chunk = 0;
-      tsamd_shard_range(cfg.n, r, cfg.world, &b, &cnt);
-      const uint32_t npad_r = (cnt + 511u) / 512u * 512u;
-      const bool fits = hybrid ? hybrid_geometry(cfg.k, npad_r, cap, &grid, &chunk) : resident_geometry(cfg.k, npad_r, cap, &grid, &chunk);
-      too_big = too_big || !fits;
-      ok = fits && grid >= (uint32_t)kResGroups;
-      if (r == cfg.rank) {
-        my_grid = grid;
-        my_chunk = chunk;
-      }
-    }
-    if (ok) break;
-    // ts_hybrid is for shards ABOVE the register capacity.  A shard too SMALL to fill 8 workgroups (up to ~1 800 individuals:
-    // not every group of every rank would post a sum) stays with one launch per pass and the peer-to-peer rows -- an
-    // untuned hybrid geometry of 16 individuals per workgroup is not what such a run should get (advisor, round 4)
-    if (hybrid || !too_big) return;
+// Replace the plan as a whole from c->in (the facts as they stand now) and hand its pass geometry to the kernels.  A plan
+// with a resident kernel needs their in-launch exchange buffer: without it the context plans as with TSAMD_RESIDENT=0.
+// (false: that buffer could not be allocated)
+bool replan(tsamd_ctx *c) {
+  c->plan = plan_launch(c->in);
+  const bool have_res = c->plan.qualified == TSAMD_LAUNCH_PER_PASS || alloc_res(c);
+  if (!have_res) {
+    c->in.knobs.resident = 0u;
+    c->plan = plan_launch(c->in);
   }
-  if (!alloc_res(c)) return;
-  c->sched_grid = my_grid;
-  c->sched_chunk = my_chunk;
-  c->hybrid = hybrid;
-  c->persistent = c->can_persistent = true;
-  // (validation-mode schedules run batched on every rank alike: ts_holblock<K, WR>, level 2 of its wide exchange in Xchg::res_wide)
-  c->can_holblock = !hybrid && kHolblockBlocksPerCu[cfg.k]() >= 1;
-  c->can_hybhol = hybrid && kHybholBlocksPerCu[cfg.k]() >= 1;  // (... ts_hybhol<K, WR> when the ranks run ts_hybrid)
+  c->p.chunk = c->plan.chunk;
+  c->p.chunk_first = c->plan.chunk_first;
+  c->p.rows_from_lt = c->plan.rows_from_lt;
+  return have_res;
+}
+
+// the kernel a resident launch of `mode` runs, for messages
+const char *resident_kernel_name(const tsamd_ctx *c, int mode) {
+  return mode == TSAMD_LAUNCH_PER_SCHEDULE ? (c->plan.family == kFamHybrid ? "ts_hybrid" : "ts_schedule") : "ts_resident";
 }
 
 // Switch the kernel sequence to the exchange buffer (rows + epoch flags pushed by every
@@ -592,7 +460,6 @@ void activate_xchg(tsamd_ctx *c) {
   c->p.xchg = c->xchg;
   c->p.xchg_world = c->cfg.world;
   c->p.xchg_rank = c->cfg.rank;
-  c->p.rows_from_lt = 0u;
   // test hooks (tsamd_device.h): honoured only by a context created with TSAMD_FLAG_TEST_HOOKS -- a stray environment
   // variable must never switch the slot-reuse guard of a production run off
   const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
@@ -603,11 +470,9 @@ void activate_xchg(tsamd_ctx *c) {
     const char *g = getenv("TSAMD_SCHEDULE_GATHER");
     c->p.xchg_gather_leaders = (g && strcmp(g, "leaders") == 0) ? 1u : 0u;
   }
-  c->split = true;
-  c->resident = c->persistent = c->can_resident = c->can_persistent = c->hybrid = c->can_holblock = c->can_hybhol = false;
-  c->p2p = true;
-  configure_launch(c, std::max<uint32_t>(16u, std::min<uint32_t>(kXchgBlocks, 512u / c->cfg.world)));
-  choose_sharded_schedule(c);
+  c->in.exchange = Exchange::kP2p;
+  c->in.knobs = read_knobs();
+  (void)replan(c);  // (without the buffer: one launch per pass and the peer-to-peer rows)
 }
 
 int alloc_xchg(tsamd_ctx *c) {
@@ -694,13 +559,7 @@ void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k)
 }
 
 void tsamd_shard_range(uint32_t n, uint32_t rank, uint32_t world, uint32_t *begin, uint32_t *count) {
-  if (world == 0) world = 1;
-  uint64_t per = ((uint64_t)n + world - 1) / world;
-  per = (per + 3) / 4 * 4;
-  uint64_t b = std::min<uint64_t>((uint64_t)rank * per, n);
-  uint64_t e = std::min<uint64_t>(b + per, n);
-  if (begin) *begin = (uint32_t)b;
-  if (count) *count = (uint32_t)(e - b);
+  shard_range(n, rank, world, begin, count);  // (tsamd_plan.h: the launch plan cuts the same shards)
 }
 
 const char *tsamd_last_error(const tsamd_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
@@ -784,16 +643,11 @@ int tsamd_create(const tsamd_config *cfg, tsamd_ctx **out) {
   // only -- every later decision (launch geometry, the sharded whole-schedule kernels, the geometry of a recovery) takes the share
   // from the context, so the ranks of a run cannot drift apart through their environments after they were created (advisor, round 5).
   // The ranks must be started with the same value; tsamd_p2p_connect_local sets it itself.
-  if (cfg->world > 1u) c->device_share = std::max<uint32_t>(1u, env_u32("TSAMD_DEVICE_SHARE", 1));
+  if (cfg->world > 1u) c->in.device_share = std::max<uint32_t>(1u, env_u32("TSAMD_DEVICE_SHARE", 1));
   c->dev = cfg->device;
   c->n_begin = b;
   c->n_local = cnt;
-  {
-    // every rank pads to the same width, so that all ranks run the same launch geometry
-    uint32_t b0 = 0, width = 0;
-    tsamd_shard_range(cfg->n, 0, cfg->world, &b0, &width);
-    c->npad = (std::max(width, cnt) + 511u) / 512u * 512u;
-  }
+  c->npad = padded_width(cfg->n, cfg->rank, cfg->world);
 #define CREATE_TRY(expr)                                                                          \
   do {                                                                                            \
     hipError_t e_ = (expr);                                                                       \
@@ -814,7 +668,6 @@ int tsamd_create(const tsamd_config *cfg, tsamd_ctx **out) {
   p.npairs = c->npad / 2;
   p.K = cfg->k;
   p.max_inner = cfg->max_inner;
-  c->split = cfg->world > 1 || (cfg->flags & TSAMD_FLAG_SPLIT_EPILOGUE);
   p.alpha = cfg->alpha;
   p.eta0 = cfg->eta0;
   p.eta1 = cfg->eta1;
@@ -823,59 +676,30 @@ int tsamd_create(const tsamd_config *cfg, tsamd_ctx **out) {
   p.gamma_scale = cfg->gamma_scale;
   p.thresh = cfg->conv_thresh;
 
-  c->wide = cfg->k > TSAMD_SPECIALIZED_K;
-  configure_launch(c, kMaxGrid);
-  if (c->wide && p.chunk_first > (uint32_t)kWideBlock * kWideItems) {
+  {
+    // the facts the launch plan depends on (tsamd_plan.h)
+    PlanInputs &in = c->in;
+    in.n = cfg->n;
+    in.k = cfg->k;
+    in.world = cfg->world;
+    in.rank = cfg->rank;
+    in.max_inner = cfg->max_inner;
+    in.nodekappa = cfg->nodekappa;
+    in.flags = cfg->flags;
+    hipDeviceProp_t prop;
+    in.cus = hipGetDeviceProperties(&prop, c->dev) == hipSuccess ? prop.multiProcessorCount : 0;
+    in.occ = probe_occupancy(cfg->k);
+    in.knobs = read_knobs();
+  }
+  if (!replan(c)) CREATE_TRY(hipErrorOutOfMemory);
+  if (c->plan.wide && p.chunk_first > (uint32_t)kWideBlock * kWideItems) {
     fail(nullptr, TSAMD_EUNSUPPORTED, "k = %u (wide-K fallback) supports at most %u individuals per GPU", cfg->k,
          (unsigned)(kMaxGrid * kWideBlock * kWideItems));
     tsamd_destroy(c);
     return TSAMD_EUNSUPPORTED;
   }
-  p.rows_from_lt = c->split ? 1u : 0u;
   p.sweep_alternate = env_u32("TSAMD_SWEEP", 1) ? 1u : 0u;
   p.probe_ticks = std::max<uint32_t>(1u, env_u32("TSAMD_PROBE_MS", 100)) * 100000u;  // (10 ns ticks)
-  {
-    // The resident kernels: one GPU (a sharded context decides in choose_sharded_schedule), K <= 32, the shard's
-    // weights fit the register file (resident_items(K) items per thread of a 256-thread workgroup) and every workgroup
-    // can be resident at once -- which the kernels verify for themselves at the start of every launch.
-    hipDeviceProp_t prop;
-    int cus = hipGetDeviceProperties(&prop, c->dev) == hipSuccess ? prop.multiProcessorCount : 0;
-    // (test hook: fewer workgroups than the device holds, so that small shards exercise the many-items-per-thread paths --
-    // ts_hybrid's LDS and streamed items for every K -- at a size the oracle finishes in a moment)
-    if ((cfg->flags & TSAMD_FLAG_TEST_HOOKS) && env_u32("TSAMD_TEST_MAX_WORKGROUPS", 0) > 0u) cus = std::min<int>(cus, (int)env_u32("TSAMD_TEST_MAX_WORKGROUPS", 0));
-    // (tuning knob, round 6's geometry sweep: at most this many workgroups for the resident kernels -- fewer members per exchange
-    // group against more individuals per thread; profiles/r06_experiments.md.  Every rank of a sharded run must see the same value)
-    if (env_u32("TSAMD_SCHED_WORKGROUPS", 0) >= (uint32_t)kResGroups) cus = std::min<int>(cus, (int)env_u32("TSAMD_SCHED_WORKGROUPS", 0));
-    c->sched_grid = c->grid;
-    c->sched_chunk = p.chunk;
-    // (TSAMD_GRID / TSAMD_BLOCK shape the launch-per-pass kernels: a context they are set for runs those)
-    const bool fits = !c->wide && cus > 0 && env_u32("TSAMD_GRID", 0) == 0u &&
-                      resident_geometry(cfg->k, c->npad, std::min<uint32_t>((uint32_t)(kResGroups * kResMembers), (uint32_t)cus), &c->sched_grid,
-                                        &c->sched_chunk, cfg->world == 1u);
-    c->res_grid = c->sched_grid;
-    c->res_chunk = c->sched_chunk;
-    if (fits)  // (ts_resident<K> instantiates its exchange with one level up to 16 workgroups at K <= 8 and never above)
-      resident_geometry(cfg->k, c->npad, std::min<uint32_t>((uint32_t)(kResGroups * kResMembers), (uint32_t)cus), &c->res_grid, &c->res_chunk,
-                        cfg->world == 1u, cfg->k <= 8u ? 16u : 0u);
-    c->resident = fits && !c->split && cfg->world == 1 && cfg->max_inner >= 2 && cfg->max_inner <= 200 &&
-                  env_u32("TSAMD_RESIDENT", 1) != 0u && kResidentBlocksPerCu[cfg->k]() >= 1;
-    // ... and then, with the reference's default learning-rate exponent (the kernel carries no pow()), the whole
-    // schedule in one launch
-    c->persistent = c->resident && cfg->nodekappa == 0.5 && env_u32("TSAMD_PERSISTENT", 1) != 0u &&
-                    kScheduleBlocksPerCu[cfg->k]() >= 1;
-    c->can_resident = c->resident;
-    c->can_persistent = c->persistent;
-    // A shard above that capacity: the same one-launch structure with part of the weights in LDS and the rest streamed
-    // (ts_hybrid) instead of ten launches per update
-    if (!fits && !c->wide && cus > 0 && !c->split && cfg->world == 1 && cfg->max_inner >= 2 && cfg->max_inner <= 200 && cfg->nodekappa == 0.5 &&
-        env_u32("TSAMD_GRID", 0) == 0u && env_u32("TSAMD_RESIDENT", 1) != 0u && env_u32("TSAMD_PERSISTENT", 1) != 0u &&
-        env_u32("TSAMD_HYBRID", 1) != 0u && kHybridBlocksPerCu[cfg->k]() >= 1 &&
-        hybrid_geometry(cfg->k, c->npad, std::min<uint32_t>((uint32_t)(kResGroups * kResMembers), (uint32_t)cus), &c->sched_grid, &c->sched_chunk)) {
-      c->hybrid = c->persistent = c->can_persistent = true;
-    }
-    c->can_holblock = c->can_persistent && !c->hybrid && cfg->world == 1u && kHolblockBlocksPerCu[cfg->k]() >= 1;  // (TSAMD_HOLBLOCK=0: read per call)
-    c->can_hybhol = c->can_persistent && c->hybrid && cfg->world == 1u && kHybholBlocksPerCu[cfg->k]() >= 1;
-  }
 
   CREATE_TRY(hipMalloc((void **)&p.bed, L * p.colstride));
   CREATE_TRY(hipMalloc((void **)&p.w, K * np * sizeof(double)));
@@ -893,7 +717,6 @@ int tsamd_create(const tsamd_config *cfg, tsamd_ctx **out) {
   CREATE_TRY(hipHostMalloc((void **)&c->h_error, (kHostDirtyWord + 1) * sizeof(unsigned long long), hipHostMallocDefault));
   memset(c->h_error, 0, (kHostDirtyWord + 1) * sizeof(unsigned long long));
   p.host_error = c->h_error;
-  if ((c->resident || c->persistent) && !alloc_res(c)) CREATE_TRY(hipErrorOutOfMemory);
   CREATE_TRY(hipMemsetAsync(p.bed, 0x55, L * p.colstride, c->stream));  // all missing
   CREATE_TRY(hipMemsetAsync(p.cnt, 0, np * sizeof(uint32_t), c->stream));
   CREATE_TRY(hipMemsetAsync(p.ctl, 0, sizeof(Ctl), c->stream));
@@ -903,14 +726,12 @@ int tsamd_create(const tsamd_config *cfg, tsamd_ctx **out) {
   // init_lambda (src/snpsamplinge.cc:239-250): lambda = eta, Elogbeta = psi(eta_t) - psi(eta0 + eta1)
   hipLaunchKernelGGL(ts_fill_f64, dim3(1024), dim3(256), 0, c->stream, p.lam, L * K * 2, cfg->eta0, cfg->eta1);
   {
-    const uint64_t total = (uint64_t)L * K;
     const uint32_t per = 1u << 20;  // locations per launch
     for (uint64_t l0 = 0; l0 < L; l0 += per) {
       const uint32_t nl = (uint32_t)std::min<uint64_t>(per, L - l0);
       hipLaunchKernelGGL(ts_export_loc, dim3(((uint64_t)nl * K + 255) / 256), dim3(256), 0, c->stream, p.lam,
                          (uint32_t)K, (uint32_t)l0, nl, 2, p.eb);
     }
-    (void)total;
   }
   CREATE_TRY(hipGetLastError());
   CREATE_TRY(hipStreamSynchronize(c->stream));
@@ -1176,10 +997,10 @@ int tsamd_set_gamma(tsamd_ctx *c, const double *gamma) {
     if (!(gamma[i] >= 1e-8) || !std::isfinite(gamma[i])) return fail(c, TSAMD_EINVAL, "gamma[%zu] must be finite and >= 1e-8", i);
   HIP_TRY(c, hipSetDevice(c->dev));
   if (int rc = upload_kmajor(c, gamma, c->p.gam, 1.0)) return rc;
-  if (c->wide)
+  if (c->plan.wide)
     hipLaunchKernelGGL(ts_refresh_w_wide, dim3((c->npad + 255) / 256), dim3(256), 0, c->stream, c->p);
   else
-    kLaunchers[c->cfg.k](kLaunchRefresh, 0, 0, c->stream, c->p, 0, 0, 0u);
+    kPass[c->cfg.k]->launch(kLaunchRefresh, 0, 0, c->stream, c->p, 0, 0, 0u);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return TSAMD_OK;
@@ -1283,12 +1104,14 @@ int tsamd_get_elogbeta(tsamd_ctx *c, uint32_t first_loc, uint32_t n_locs, double
   return export_loc(c, first_loc, n_locs, 1, out);
 }
 
-// Enqueue n schedule entries (location | hol << 31) that lie in pinned host memory, the way the context launches now.
+// Enqueue n schedule entries (location | hol << 31) that lie in pinned host memory in launch mode `mode` (the context's, or
+// TSAMD_LAUNCH_PER_SNP for one call of the single-update route, or TSAMD_LAUNCH_PER_PASS for a replay).
 // Everything that varies per SNP is read from device memory, so in the launch-per-pass mode captured sequences of
 // 16, 8, 4, 2 and 1 SNPs are replayed as often as the schedule length needs (binary decomposition: nothing is padded);
 // results are identical to eager launches bit for bit.  eager: no graphs (the replay after a failed resident launch).
-static int enqueue_entries(tsamd_ctx *c, const uint32_t *ent, uint32_t n, bool eager, tsamd_ctx::Journal *jr = nullptr) {
-  if (c->persistent) {
+static int enqueue_entries(tsamd_ctx *c, int mode, const uint32_t *ent, uint32_t n, bool eager, tsamd_ctx::Journal *jr = nullptr) {
+  if (mode == TSAMD_LAUNCH_PER_SCHEDULE) {
+    const LaunchPlan &pl = c->plan;
     // one launch runs the whole schedule (in pieces of kScheduleChunk SNPs): the kernel reads the entries straight from
     // the pinned buffer, one SNP ahead of their use; it starts from the State the previous call left and leaves one like
     // ts_flush does -- no ts_begin, no ts_flush, and none of the graphs of the launch-per-pass sequence
@@ -1301,8 +1124,8 @@ static int enqueue_entries(tsamd_ctx *c, const uint32_t *ent, uint32_t n, bool e
         HIP_TRY(c, hipEventRecord(e, c->stream));
       }
       if (jr) jr->launch_off.push_back(off);
-      (hol_block ? (c->hybrid ? kHybholLaunchers : kHolblockLaunchers) : c->hybrid ? kHybridLaunchers : kScheduleLaunchers)[c->cfg.k](
-          c->sched_grid, c->sched_chunk, c->stream, c->p, next_parity(c), ent + off, len, c->launch_serial++);
+      kWhole[hol_block ? batched_form(pl.family) : pl.family][c->cfg.k]->launch(pl.schedule.grid, pl.schedule.chunk, c->stream, c->p, next_parity(c),
+                                                                                ent + off, len, c->launch_serial++);
       if (hol_block) {
         c->holblock_launches++;
         c->holblock_locs += len;
@@ -1321,7 +1144,7 @@ static int enqueue_entries(tsamd_ctx *c, const uint32_t *ent, uint32_t n, bool e
     // precedes it: that is where the pending gamma step is applied (src/snpsamplinge.cc:660-668).
     // (a context that runs ts_hybrid -- the shard exceeds the register capacity -- batches with ts_hybhol, which shares the
     // streamed weights across the locations of a sub-batch as well as the exchange; its first entry goes through ts_hybrid)
-    if ((ent[0] >> 31) != 0u && (c->can_holblock || c->can_hybhol) && env_u32("TSAMD_HOLBLOCK", 1) != 0u && n >= (c->tail_step_pending ? 3u : 2u)) {
+    if ((ent[0] >> 31) != 0u && pl.batch_validation && env_u32("TSAMD_HOLBLOCK", 1) != 0u && n >= (c->tail_step_pending ? 3u : 2u)) {
       if (c->tail_step_pending) {
         if (int rc = launch(false, 0u, 1u)) return rc;
         off = 1u;
@@ -1350,13 +1173,13 @@ static int enqueue_entries(tsamd_ctx *c, const uint32_t *ent, uint32_t n, bool e
     HIP_TRY(c, hipMalloc((void **)&c->d_sched, (size_t)cap * sizeof(uint32_t)));
     c->sched_cap = cap;  // (the kernels take the pointer from Ctl, written by ts_begin)
   }
-  const bool use_graph = !eager && graphs_allowed(c);
+  const bool use_graph = !eager && graphs_allowed(c, mode);
   if (use_graph)
     if (int rc = ensure_graphs(c)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_sched, ent, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   enqueue_begin(c, n, false);
   if (use_graph) {
-    const uint32_t per_snp = kernels_per_snp(c);
+    const uint32_t per_snp = kernels_per_snp(mode, c->cfg.max_inner);
     uint32_t left = n;
     auto replay = [&](uint32_t level) -> int {
       HIP_TRY(c, hipGraphLaunch(c->graphs[level][c->q & 1u].exec, c->stream));
@@ -1373,10 +1196,10 @@ static int enqueue_entries(tsamd_ctx *c, const uint32_t *ent, uint32_t n, bool e
     for (int level = (int)kGraphLevels - 1; level >= 0; --level)
       while (left >= (1u << level))
         if (int rc = replay((uint32_t)level)) return rc;
-    c->prev_rows = c->cfg.max_inner > 1 ? c->grid : c->grid_first;
+    c->prev_rows = c->cfg.max_inner > 1 ? c->plan.grid : c->plan.grid_first;
   } else {
     for (uint32_t i = 0; i < n; ++i)
-      if (int rc = enqueue_snp(c)) return rc;
+      if (int rc = enqueue_snp(c, mode == TSAMD_LAUNCH_PER_SNP)) return rc;
   }
   enqueue_flush(c);
   HIP_TRY(c, hipGetLastError());
@@ -1410,7 +1233,7 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
   const bool was_persistent = c->journal[at].mode == 2;
   *(volatile unsigned long long *)c->h_error = 0ull;
   HIP_TRY(c, hipMemsetAsync(c->res, 0, sizeof(ResXchg), c->stream));  // the abort word, and the granules of the failed exchange
-  if (c->p2p) {
+  if (p2p(c)) {
     // the failed exchange's granules in the ranks' res_sums keep its tag, and peers may still be storing them: the next
     // resident launch (after tsamd_set_launch_mode raises the mode again) must not take them for its own -- skip the tags
     uint32_t xseq = 0;
@@ -1420,9 +1243,11 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
     HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->xseq, &xseq, sizeof xseq, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  c->resident = c->persistent = false;
+  const char *failed_kernel = resident_kernel_name(c, c->journal[at].mode);
+  const uint32_t failed_grid = c->plan.schedule.grid;
+  c->plan.mode = TSAMD_LAUNCH_PER_PASS;
   destroy_graph(c);
-  if (c->p2p) {
+  if (p2p(c)) {
     // Ranks that SHARE this device (tests, rehearsals): the resident launch failed because something holds compute units, and
     // the pass kernels of the replay spin in their prologues until every rank's previous pass has delivered its rows -- the
     // ranks' kernels must fit what is LEFT of the device together, or a rank's waiting workgroups keep its peers' previous
@@ -1430,15 +1255,17 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
     // compute units, one run in two).  The replay therefore runs on an eighth of each rank's share (every rank takes this
     // branch alike: the exchange's row layout stays consistent).  One rank per device: a pass kernel never waits for a
     // kernel that needs the same device, nothing to do.
-    const uint32_t share = std::max<uint32_t>(1u, c->device_share);
+    const uint32_t share = std::max<uint32_t>(1u, c->in.device_share);
     if (share > 1u) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, c->dev) != hipSuccess || prop.multiProcessorCount <= 0) {
+      if (c->in.cus <= 0) {
         // (a rank that kept its grid while its peers shrank theirs would read mismatched rows: no silent skip)
         c->recovering = false;
         return fail(c, TSAMD_EHIP, "replay after a failed resident launch: cannot query device %d to size the replay's launches", c->dev);
       }
-      configure_launch(c, std::max<uint32_t>(4u, (uint32_t)prop.multiProcessorCount / (8u * share)));
+      c->in.pass_grid_cap = std::max<uint32_t>(4u, (uint32_t)c->in.cus / (8u * share));
+      c->in.knobs = read_knobs();
+      (void)replan(c);
+      c->plan.mode = TSAMD_LAUNCH_PER_PASS;
       shrunk = true;
     }
   }
@@ -1448,7 +1275,7 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
     const tsamd_ctx::Journal &j = c->journal[at];
     if (was_persistent) {
       const uint32_t off = j.launch_off[ahead];  // (first entry of the launch that gave up: ts_schedule's or ts_holblock's)
-      rc = enqueue_entries(c, j.ent + off, j.n - off, true);
+      rc = enqueue_entries(c, TSAMD_LAUNCH_PER_PASS, j.ent + off, j.n - off, true);
     } else {
       // ts_resident of SNP st.idx of this schedule: its first pass is done and pending (rows in the same slot); run its
       // plain passes, then the rest of the schedule
@@ -1471,13 +1298,13 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
         HIP_TRY(c, hipMemcpyAsync(&c->p.ctl->sched_len, &len, sizeof len, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the sources are on this stack frame)
       }
-      c->prev_rows = c->grid_first;
+      c->prev_rows = c->plan.grid_first;
       for (uint32_t i = 1; rc == TSAMD_OK && i < c->cfg.max_inner; ++i) rc = enqueue_pass(c, i);
-      for (uint32_t sn = st.idx + 1u; rc == TSAMD_OK && sn < j.n; ++sn) rc = enqueue_snp(c);
+      for (uint32_t sn = st.idx + 1u; rc == TSAMD_OK && sn < j.n; ++sn) rc = enqueue_snp(c, false);
       if (rc == TSAMD_OK) enqueue_flush(c);
     }
   }
-  for (size_t i = at + 1; rc == TSAMD_OK && i < c->journal.size(); ++i) rc = enqueue_entries(c, c->journal[i].ent, c->journal[i].n, true);
+  for (size_t i = at + 1; rc == TSAMD_OK && i < c->journal.size(); ++i) rc = enqueue_entries(c, TSAMD_LAUNCH_PER_PASS, c->journal[i].ent, c->journal[i].n, true);
   if (rc == TSAMD_OK) {
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail(c, TSAMD_EHIP, "replay after a failed resident launch: %s", hipGetErrorString(e));
@@ -1488,7 +1315,7 @@ static int recover_from_failed_entry(tsamd_ctx *c, unsigned long long code) {
   c->recoveries++;
   fail(c, TSAMD_OK, "warning: %s could not get its %u workgroups resident at once (something else holds compute units of device %d); the "
        "schedule was replayed one launch per pass from the unchanged state and the context stays in that mode "
-       "(tsamd_set_launch_mode raises it again)%s", was_persistent ? (c->hybrid ? "ts_hybrid" : "ts_schedule") : "ts_resident", c->sched_grid, c->dev,
+       "(tsamd_set_launch_mode raises it again)%s", failed_kernel, failed_grid, c->dev,
        shrunk ? "; ranks sharing the device: the launch-per-pass kernels keep the reduced geometry of the replay (an eighth of each rank's share) from here on" : "");
   return TSAMD_OK;
 }
@@ -1503,29 +1330,30 @@ static int settle(tsamd_ctx *c) {
     // (a workgroup that passed the entry exchange, modified state and only then met the abort word leaves its code here:
     // the launch did NOT give up as a whole with its state intact, whatever the first word says)
     const bool dirty = *(volatile unsigned long long *)(c->h_error + kHostDirtyWord) != 0ull;
+    const bool persistent = c->plan.mode == TSAMD_LAUNCH_PER_SCHEDULE;
     if (getenv("TSAMD_DEBUG"))
       fprintf(stderr, "[tsamd rank %u] settle: error word %llx (tag %llu, intact %d, parity %d, serial %llu), modified-state word %llx, journal %zu, "
               "launch serial %u, mode %d/%d\n", c->cfg.rank, err, tag, (int)((err & kFailIntact) != 0ull), (int)((err >> 33) & 1ull), err >> 34,
-              *(volatile unsigned long long *)(c->h_error + kHostDirtyWord), c->journal.size(), c->launch_serial, (int)c->resident, (int)c->persistent);
+              *(volatile unsigned long long *)(c->h_error + kHostDirtyWord), c->journal.size(), c->launch_serial, (int)c->plan.resident_passes(c->plan.mode), (int)persistent);
     // (a sharded context, one process per rank: the entry exchange spans the ranks, so it fails on EVERY rank -- nobody has
     // written anything -- and every rank, driven by the same calls, finds the same launch in its journal and replays the
     // same kernels.  Contexts of ONE process (tsamd_p2p_connect_local) are settled one after the other and would wait for
     // a peer's replay that has not been enqueued yet: they keep reporting TSAMD_ECOMM.)
     if (tag == 0xffffffffull)  // (tested first: on a sharded context the exchange branches below would report it as a peer that did not arrive)
       rc = fail(c, TSAMD_EHIP, "internal error: ts_holblock was launched with a gamma step pending (the state is intact; the context is not usable)");
-    else if ((err & kFailIntact) != 0ull && !dirty && (c->cfg.world == 1u || (c->p2p && c->persistent && !c->peer_maps.empty())) && c->res && !c->recovering)
+    else if ((err & kFailIntact) != 0ull && !dirty && (c->cfg.world == 1u || (p2p(c) && persistent && !c->peer_maps.empty())) && c->res && !c->recovering)
       rc = recover_from_failed_entry(c, err);
-    else if (c->p2p && (c->persistent || (err & kFailIntact) != 0ull))
+    else if (p2p(c) && (persistent || (err & kFailIntact) != 0ull))
       rc = fail(c, TSAMD_ECOMM, "ts_schedule: the in-launch exchange across %u ranks timed out (tag %llu): a peer did not arrive, or "
                 "not all workgroups of all ranks are resident (ranks that share one device: TSAMD_DEVICE_SHARE=<ranks>) [code %llx, "
                 "modified-state word %llx, whole-schedule mode %d, mapped peers %zu]",
-                c->cfg.world, tag, err, *(volatile unsigned long long *)(c->h_error + kHostDirtyWord), (int)c->persistent, c->peer_maps.size());
-    else if (c->p2p)
+                c->cfg.world, tag, err, *(volatile unsigned long long *)(c->h_error + kHostDirtyWord), (int)persistent, c->peer_maps.size());
+    else if (p2p(c))
       rc = fail(c, TSAMD_ECOMM, "peer-to-peer exchange timed out waiting for a peer (epoch %llu)", err);
     else
       rc = fail(c, TSAMD_EHIP, "%s: the in-launch exchange timed out in the middle of a launch (tag %llu, %u workgroups): the state is void.  "
                 "TSAMD_PERSISTENT=0 selects one launch per SNP for the plain passes, TSAMD_RESIDENT=0 one launch per pass",
-                c->persistent ? (c->hybrid ? "ts_hybrid" : "ts_schedule") : "ts_resident", tag, c->sched_grid);
+                resident_kernel_name(c, c->plan.mode), tag, c->plan.schedule.grid);
   }
   for (auto &j : c->journal) {
     c->sched_free.push_back({j.ent, j.cap});
@@ -1538,7 +1366,7 @@ int tsamd_run_schedule(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int hol_m
   CHECK_CTX(c);
   if (n == 0) return TSAMD_OK;
   if (!locs) return fail(c, TSAMD_EINVAL, "null schedule");
-  if (c->cfg.world > 1 && !c->comm && !c->p2p)
+  if (c->cfg.world > 1 && !c->comm && !p2p(c))
     return fail(c, TSAMD_ECOMM, "context is shard %u of %u but neither tsamd_comm_init nor tsamd_p2p_connect has been called",
                 c->cfg.rank, c->cfg.world);
   for (uint32_t i = 0; i < n; ++i)
@@ -1548,9 +1376,9 @@ int tsamd_run_schedule(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int hol_m
   // A peer-to-peer context cannot simply wait here (its kernels wait for peers the caller may not have enqueued yet): it
   // drops the entries whose kernels have finished -- an event per entry, queried, never waited for -- as long as no kernel
   // has reported anything (a failed launch is replayed from its own entry onwards: earlier ones are not needed)
-  if (!c->p2p && c->journal.size() >= 256)
+  if (!p2p(c) && c->journal.size() >= 256)
     if (int rc = settle(c)) return rc;
-  if (c->p2p && c->journal.size() >= 256) {
+  if (p2p(c) && c->journal.size() >= 256) {
     size_t drop = 0;
     while (drop < c->journal.size() && c->journal[drop].done && hipEventQuery(c->journal[drop].done) == hipSuccess &&
            *(volatile unsigned long long *)c->h_error == 0ull)
@@ -1568,14 +1396,11 @@ int tsamd_run_schedule(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int hol_m
   // half of gamma and writing them back around ONE update; from about 4M weights per GPU on, the launch-per-SNP
   // sequence is the faster route for such a call (N = 1M, K = 8: 7 830 against 6 860 calls/s; N = 125K, K = 20: 8 200
   // against 9 430, tools/single_update_rate.py).  The State either sequence leaves is the other's start.
-  const bool single_route = n == 1u && c->persistent && c->can_resident && (uint64_t)c->n_local * c->cfg.k >= (4ull << 20) &&
-                            env_u32("TSAMD_SINGLE_ROUTE", 1) != 0u;
-  if (single_route) {
-    c->persistent = false;
-    c->resident = true;
-  }
+  const bool single_route = n == 1u && c->plan.mode == TSAMD_LAUNCH_PER_SCHEDULE && c->plan.qualifies(TSAMD_LAUNCH_PER_SNP) &&
+                            (uint64_t)c->n_local * c->cfg.k >= (4ull << 20) && env_u32("TSAMD_SINGLE_ROUTE", 1) != 0u;
+  const int mode = single_route ? TSAMD_LAUNCH_PER_SNP : c->plan.mode;
   // the schedule goes up through a pinned buffer: the copy is then really asynchronous
-  tsamd_ctx::Journal j{nullptr, 0, n, c->launch_serial, c->persistent ? 2 : c->resident ? 1 : 0, {}, nullptr};
+  tsamd_ctx::Journal j{nullptr, 0, n, c->launch_serial, mode, {}, nullptr};
   for (size_t i = 0; i < c->sched_free.size(); ++i)
     if (c->sched_free[i].second >= n) {
       j.ent = c->sched_free[i].first;
@@ -1587,17 +1412,15 @@ int tsamd_run_schedule(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int hol_m
     size_t cap = 1024;
     while (cap < n) cap *= 2;
     // (portable + mapped: ts_schedule reads the entries straight from this buffer, on whichever device the context uses)
-    if (hipHostMalloc((void **)&j.ent, cap * sizeof(uint32_t), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) {
-      if (single_route) c->persistent = true;
+    if (hipHostMalloc((void **)&j.ent, cap * sizeof(uint32_t), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
       return fail(c, TSAMD_ENOMEM, "hipHostMalloc of a %zu-entry schedule buffer failed", cap);
-    }
     j.cap = cap;
   }
   c->journal.push_back(j);
   for (uint32_t i = 0; i < n; ++i) j.ent[i] = locs[i] | (hol_mode ? 0x80000000u : 0u);
-  int rc = enqueue_entries(c, j.ent, n, false, &c->journal.back());
+  int rc = enqueue_entries(c, mode, j.ent, n, false, &c->journal.back());
   if (rc == TSAMD_OK) c->tail_step_pending = hol_mode == 0;  // (what was actually enqueued: a failed call leaves the flag as it was)
-  if (rc == TSAMD_OK && c->p2p) {
+  if (rc == TSAMD_OK && p2p(c)) {
     hipEvent_t ev = nullptr;
     if (!c->event_free.empty()) {
       ev = c->event_free.back();
@@ -1608,22 +1431,21 @@ int tsamd_run_schedule(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int hol_m
     }
     if (ev && hipEventRecord(ev, c->stream) == hipSuccess) c->journal.back().done = ev;
   }
-  if (single_route) c->persistent = true;  // (c->resident stays set: it is what the mode falls back to when lowered by one)
   return rc;
 }
 
 int tsamd_prepare(tsamd_ctx *c) {
   CHECK_CTX(c);
   HIP_TRY(c, hipSetDevice(c->dev));
-  if (c->cfg.world > 1 && !c->comm && !c->p2p) return TSAMD_OK;  // exchange not chosen yet: nothing to capture
-  if (c->persistent) {  // an empty schedule: the kernel's code object is loaded, the state only carried forward
-    (c->hybrid ? kHybridLaunchers : kScheduleLaunchers)[c->cfg.k](c->sched_grid, c->sched_chunk, c->stream, c->p, next_parity(c), c->d_sched, 0u,
-                                                                  c->launch_serial++);
+  if (c->cfg.world > 1 && !c->comm && !p2p(c)) return TSAMD_OK;  // exchange not chosen yet: nothing to capture
+  if (c->plan.mode == TSAMD_LAUNCH_PER_SCHEDULE) {  // an empty schedule: the kernel's code object is loaded, the state only carried forward
+    kWhole[c->plan.family][c->cfg.k]->launch(c->plan.schedule.grid, c->plan.schedule.chunk, c->stream, c->p, next_parity(c), c->d_sched, 0u,
+                                             c->launch_serial++);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return TSAMD_OK;
   }
-  if (!graphs_allowed(c)) return TSAMD_OK;
+  if (!graphs_allowed(c, c->plan.mode)) return TSAMD_OK;
   if (int rc = ensure_graphs(c)) return rc;
   // One dry replay of every graph: whatever the runtime does on a graph's first launch happens
   // here.  With no schedule in progress every kernel of the sequence only carries the state
@@ -1634,7 +1456,7 @@ int tsamd_prepare(tsamd_ctx *c) {
     for (uint32_t par0 = 0; par0 < 2; ++par0) {
       if ((uint32_t)(c->q & 1u) != par0) enqueue_begin(c, 0xffffffffu, false);
       HIP_TRY(c, hipGraphLaunch(c->graphs[level][par0].exec, c->stream));
-      c->q += (uint64_t)(1u << level) * kernels_per_snp(c);
+      c->q += (uint64_t)(1u << level) * kernels_per_snp(c->plan.mode, c->cfg.max_inner);
     }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return TSAMD_OK;
@@ -1649,7 +1471,7 @@ int tsamd_synchronize(tsamd_ctx *c) {
       if (hipEventElapsedTime(&ms, c->ev_pass[2 * i], c->ev_pass[2 * i + 1]) == hipSuccess) {
         c->prof_pass_ms += ms;
         // launches inside the bracket (profile_read corrects for no-ops); ts_schedule: the bracket is one launch
-        c->prof_pass_n += c->persistent ? 1u : c->cfg.max_inner - 1;
+        c->prof_pass_n += c->plan.mode == TSAMD_LAUNCH_PER_SCHEDULE ? 1u : c->cfg.max_inner - 1;
       }
     }
     for (uint32_t i = 0; i < c->n_ev_first; ++i) {
@@ -1820,9 +1642,8 @@ int tsamd_comm_init(tsamd_ctx *c, const uint8_t id[TSAMD_COMM_ID_BYTES]) {
     c->comm = nullptr;
     return fail(c, TSAMD_ECOMM, "ncclCommInitRank: %s", g_rccl.GetErrorString(r));
   }
-  c->split = true;
-  c->resident = c->persistent = c->can_resident = c->can_persistent = c->hybrid = c->can_holblock = c->can_hybhol = false;
-  c->p.rows_from_lt = 1u;
+  c->in.exchange = Exchange::kRccl;  // (one launch per pass, on the geometry the context was created with)
+  (void)replan(c);
   c->rccl_graph = env_u32("TSAMD_RCCL_GRAPH", 0) != 0u;
   destroy_graph(c);
   return TSAMD_OK;
@@ -1845,7 +1666,7 @@ int tsamd_p2p_connect(tsamd_ctx *c, const uint8_t *handles) {
   CHECK_CTX(c);
   if (!handles) return fail(c, TSAMD_EINVAL, "null handles");
   if (!c->xchg) return fail(c, TSAMD_EINVAL, "tsamd_p2p_export has not been called");
-  if (c->p2p) return fail(c, TSAMD_EINVAL, "peer-to-peer exchange already connected");
+  if (p2p(c)) return fail(c, TSAMD_EINVAL, "peer-to-peer exchange already connected");
   HIP_TRY(c, hipSetDevice(c->dev));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (uint32_t q = 0; q < c->cfg.world; ++q) {
@@ -1866,7 +1687,7 @@ int tsamd_p2p_connect(tsamd_ctx *c, const uint8_t *handles) {
     c->p.peers[q] = (Xchg *)ptr;
   }
   activate_xchg(c);
-  if (c->wide && c->p.chunk_first > (uint32_t)kWideBlock * kWideItems)
+  if (c->plan.wide && c->p.chunk_first > (uint32_t)kWideBlock * kWideItems)
     return fail(c, TSAMD_EUNSUPPORTED, "wide-K fallback: shard too large for the peer-to-peer launch geometry");
   destroy_graph(c);
   return TSAMD_OK;
@@ -1883,7 +1704,7 @@ int tsamd_p2p_connect_local(tsamd_ctx *const *ctxs, uint32_t count) {
     if (!c) return fail(c0, TSAMD_EINVAL, "null context %u", i);
     if (c->cfg.world != count || c->cfg.rank >= count || by_rank[c->cfg.rank])
       return fail(c0, TSAMD_EINVAL, "contexts must be the ranks 0..%u of a world of %u, once each", count - 1, count);
-    if (c->p2p || c->comm) return fail(c0, TSAMD_EINVAL, "context of rank %u already has an exchange", c->cfg.rank);
+    if (p2p(c) || c->comm) return fail(c0, TSAMD_EINVAL, "context of rank %u already has an exchange", c->cfg.rank);
     if (c->cfg.n != c0->cfg.n || c->cfg.k != c0->cfg.k || c->cfg.l != c0->cfg.l)
       return fail(c0, TSAMD_EINVAL, "contexts differ in n / l / k");
     by_rank[c->cfg.rank] = c;
@@ -1913,9 +1734,9 @@ int tsamd_p2p_connect_local(tsamd_ctx *const *ctxs, uint32_t count) {
   for (tsamd_ctx *c : by_rank) {
     HIP_TRY(c, hipSetDevice(c->dev));
     for (uint32_t q = 0; q < count; ++q) c->p.peers[q] = by_rank[q]->xchg;
-    c->device_share = share;
+    c->in.device_share = share;
     activate_xchg(c);
-    if (c->wide && c->p.chunk_first > (uint32_t)kWideBlock * kWideItems)
+    if (c->plan.wide && c->p.chunk_first > (uint32_t)kWideBlock * kWideItems)
       return fail(c, TSAMD_EUNSUPPORTED, "wide-K fallback: shard too large for the peer-to-peer launch geometry");
     destroy_graph(c);
   }
@@ -1987,7 +1808,7 @@ int tsamd_profile_read(tsamd_ctx *c, uint64_t *pass_launches, double *pass_ms_to
   // plain passes that really swept: the passes the device counted since profiling was enabled
   // minus the first passes (a SNP that converges early leaves near-empty launches inside its
   // bracket; dividing by them would overstate the rate)
-  if (!c->prof_capped && c->prof_first_n && !c->persistent) {
+  if (!c->prof_capped && c->prof_first_n && c->plan.mode != TSAMD_LAUNCH_PER_SCHEDULE) {
     const unsigned long long v = *(volatile unsigned long long *)(c->h_error + 2);
     const uint64_t ran = v - c->prof_passes0;
     if (ran >= c->prof_first_n && ran - c->prof_first_n <= c->prof_pass_n) c->prof_pass_n = ran - c->prof_first_n;
@@ -2009,16 +1830,16 @@ int tsamd_probe_stream(tsamd_ctx *c, uint32_t reps, double *read_us, double *rmw
   HIP_TRY(c, hipEventCreate(&e1));
   double *sink = c->p.partials;  // never written: the probe's condition cannot hold
   const uint32_t K = c->cfg.k;
-  const uint32_t chunk_first = (!c->wide && c->first_vec == 2) ? c->p.chunk_first * 2u : c->p.chunk_first;  // individuals
-  const uint32_t chunk_pairs = c->wide ? (c->p.chunk + 1u) / 2u : c->p.chunk;
+  const uint32_t chunk_first = (!c->plan.wide && c->plan.first_vec == 2) ? c->p.chunk_first * 2u : c->p.chunk_first;  // individuals
+  const uint32_t chunk_pairs = c->plan.wide ? (c->p.chunk + 1u) / 2u : c->p.chunk;
   auto timed = [&](bool rmw, double *out_us) -> hipError_t {
     for (uint32_t r = 0; r < 3u + reps; ++r) {
       if (r == 3u) (void)hipEventRecord(e0, c->stream);
       if (rmw)
-        hipLaunchKernelGGL(ts_probe_rmw, dim3(c->grid_first), dim3(256), 0, c->stream, c->p.w, c->p.gam, K, c->npad,
+        hipLaunchKernelGGL(ts_probe_rmw, dim3(c->plan.grid_first), dim3(256), 0, c->stream, c->p.w, c->p.gam, K, c->npad,
                            chunk_first, 1.0, env_u32("TSAMD_PROBE_THINK_NS", 0) / 10u);
       else
-        hipLaunchKernelGGL(ts_probe_read, dim3(c->grid), dim3(c->block), 0, c->stream, c->p.w, K, c->npad, chunk_pairs,
+        hipLaunchKernelGGL(ts_probe_read, dim3(c->plan.grid), dim3(c->plan.block), 0, c->stream, c->p.w, K, c->npad, chunk_pairs,
                            c->p.sweep_alternate ? (r & 1u) : 0u, sink);
     }
     hipError_t e = hipEventRecord(e1, c->stream);
@@ -2038,9 +1859,9 @@ int tsamd_probe_stream(tsamd_ctx *c, uint32_t reps, double *read_us, double *rmw
 
 int tsamd_launch_info(tsamd_ctx *c, uint32_t *kernels_per_snp_out, uint32_t *plain_grid, uint32_t *first_grid) {
   CHECK_CTX(c);
-  if (kernels_per_snp_out) *kernels_per_snp_out = c->persistent ? 0u : kernels_per_snp(c);
-  if (plain_grid) *plain_grid = c->grid;
-  if (first_grid) *first_grid = c->grid_first;
+  if (kernels_per_snp_out) *kernels_per_snp_out = kernels_per_snp(c->plan.mode, c->cfg.max_inner);
+  if (plain_grid) *plain_grid = c->plan.grid;
+  if (first_grid) *first_grid = c->plan.grid_first;
   return TSAMD_OK;
 }
 
@@ -2048,25 +1869,21 @@ int tsamd_schedule_geometry(tsamd_ctx *c, int mode, uint32_t *workgroups, uint32
                             uint32_t *on_chip_per_thread) {
   CHECK_CTX(c);
   if (mode != TSAMD_LAUNCH_PER_SNP && mode != TSAMD_LAUNCH_PER_SCHEDULE) return fail(c, TSAMD_EINVAL, "launch mode %d has no resident kernel", mode);
-  if ((mode == TSAMD_LAUNCH_PER_SNP && !c->can_resident) || (mode == TSAMD_LAUNCH_PER_SCHEDULE && !c->can_persistent))
-    return fail(c, TSAMD_EUNSUPPORTED, "the context does not qualify for launch mode %d", mode);
-  const bool sched = mode == TSAMD_LAUNCH_PER_SCHEDULE;
-  const uint32_t grid = sched ? c->sched_grid : c->res_grid, chunk = sched ? c->sched_chunk : c->res_chunk;
-  const uint32_t one = sched ? (uint32_t)kResOneLevelGrid : (c->cfg.k <= 8u ? 16u : 0u);
-  if (workgroups) *workgroups = grid;
-  if (indivs_per_thread) *indivs_per_thread = (chunk + (uint32_t)kResidentBlock - 1u) / (uint32_t)kResidentBlock * (uint32_t)resident_vec((int)c->cfg.k);
-  if (exchange_levels) *exchange_levels = (grid == 1u && c->cfg.world == 1u) ? 0u : (c->cfg.world == 1u && grid <= one) ? 1u : 2u;
-  if (on_chip_per_thread) {
-    const uint32_t per = (chunk + (uint32_t)kResidentBlock - 1u) / (uint32_t)kResidentBlock * (uint32_t)resident_vec((int)c->cfg.k);
-    *on_chip_per_thread = (sched && c->hybrid) ? std::min<uint32_t>(per, (uint32_t)(hy_reg_items((int)c->cfg.k) + hy_lds_items((int)c->cfg.k))) : per;
-  }
+  if (!c->plan.qualifies(mode)) return fail(c, TSAMD_EUNSUPPORTED, "the context does not qualify for launch mode %d", mode);
+  const ResidentGeometry &g = mode == TSAMD_LAUNCH_PER_SCHEDULE ? c->plan.schedule : c->plan.snp;
+  if (workgroups) *workgroups = g.grid;
+  if (indivs_per_thread) *indivs_per_thread = g.indivs_per_thread;
+  if (exchange_levels) *exchange_levels = g.exchange_levels;
+  if (on_chip_per_thread) *on_chip_per_thread = g.on_chip_per_thread;
   return TSAMD_OK;
 }
 
 int tsamd_holblock_info(tsamd_ctx *c, uint32_t *batch, uint64_t *launches, uint64_t *locations) {
   CHECK_CTX(c);
   if (batch)
-    *batch = (c->persistent && env_u32("TSAMD_HOLBLOCK", 1) != 0u) ? (c->can_holblock ? (uint32_t)hol_batch((int)c->cfg.k) : c->can_hybhol ? (uint32_t)kHybholBatch[c->cfg.k]() : 0u) : 0u;
+    *batch = (c->plan.mode == TSAMD_LAUNCH_PER_SCHEDULE && c->plan.batch_validation && env_u32("TSAMD_HOLBLOCK", 1) != 0u)
+                 ? (uint32_t)kWhole[batched_form(c->plan.family)][c->cfg.k]->batch
+                 : 0u;
   if (launches) *launches = c->holblock_launches;
   if (locations) *locations = c->holblock_locs;
   return TSAMD_OK;
@@ -2075,15 +1892,14 @@ int tsamd_holblock_info(tsamd_ctx *c, uint32_t *batch, uint64_t *launches, uint6
 int tsamd_set_launch_mode(tsamd_ctx *c, int mode) {
   CHECK_CTX(c);
   if (mode < TSAMD_LAUNCH_PER_PASS || mode > TSAMD_LAUNCH_PER_SCHEDULE) return fail(c, TSAMD_EINVAL, "launch mode %d", mode);
-  if ((mode == TSAMD_LAUNCH_PER_SNP && !c->can_resident) || (mode == TSAMD_LAUNCH_PER_SCHEDULE && !c->can_persistent))
+  if (!c->plan.qualifies(mode))
     return fail(c, TSAMD_EUNSUPPORTED, "launch mode %d needs k <= %d, a shard that fits the register file (%d individuals per workgroup at k = %u)%s",
                 mode, kResidentMaxK, (int)c->cfg.k <= kResidentMaxK ? resident_capacity((int)c->cfg.k) : 0, c->cfg.k,
                 mode == TSAMD_LAUNCH_PER_SCHEDULE ? " and nodekappa == 0.5" : " and one GPU");
   if (int rc = tsamd_synchronize(c)) return rc;
-  const bool resident = mode >= TSAMD_LAUNCH_PER_SNP && c->can_resident, persistent = mode == TSAMD_LAUNCH_PER_SCHEDULE;
-  if (resident != c->resident) destroy_graph(c);  // (captured for the other kernel sequence)
-  c->resident = resident;  // (a sharded context has no launch-per-SNP mode: ts_schedule or one launch per pass)
-  c->persistent = persistent;
+  // (a sharded context has no launch-per-SNP mode: ts_schedule or one launch per pass)
+  if (c->plan.resident_passes(mode) != c->plan.resident_passes(c->plan.mode)) destroy_graph(c);  // (captured for the other kernel sequence)
+  c->plan.mode = mode;
   return TSAMD_OK;
 }
 

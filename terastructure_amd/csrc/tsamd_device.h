@@ -14,11 +14,11 @@
 #include <stdint.h>
 
 #include "tsamd.h"
+#include "tsamd_capacity.h"
 
 namespace tsamd {
 
 constexpr int kBlock = 256;       // threads per workgroup of the generic kernels
-constexpr int kMaxGrid = 2048;    // upper bound on pass-kernel workgroups
 
 // Device-resident state machine.  No workgroup ever reads a word that another workgroup
 // of the SAME launch writes: every kernel of the stream-ordered sequence carries a parity
@@ -71,9 +71,7 @@ struct Ctl {
 // release; the next launch's prologue waits for world * nblk flags and adds the rows in
 // that fixed order.  Pass kernels then run with at most 512 / world workgroups (every
 // workgroup of the next launch polls all flags and re-adds all rows), never more than
-// kXchgBlocks.
-constexpr int kMaxRanks = 16;
-constexpr int kXchgBlocks = 256;
+// kXchgBlocks (tsamd_capacity.h).
 struct Xchg {
   double rows[2][kMaxRanks * kXchgBlocks * 2 * TSAMD_MAX_K];
   unsigned long long seq[2][kMaxRanks * kXchgBlocks];

@@ -1,12 +1,7 @@
 // The batched validation-mode kernel for shards above the register capacity, ts_hybhol<K> (tsamd_hybhol_kernels.h), one
 // translation unit per K <= kResidentMaxK, compiled with -DTSAMD_K=<k> (terastructure_amd/build.py).
 #include "tsamd_hybhol_kernels.h"
-
-#ifndef TSAMD_K
-#error "compile with -DTSAMD_K=<populations>"
-#endif
-#define TSAMD_CAT2(a, b) a##b
-#define TSAMD_CAT(a, b) TSAMD_CAT2(a, b)
+#include "tsamd_unit.h"
 
 namespace tsamd {
 
@@ -15,8 +10,8 @@ static_assert(hh_reg_items(TSAMD_K) + hh_lds_items(TSAMD_K) >= 1, "at least one 
 
 // n hol-mode entries at `sched` (pinned host memory), pairwise distinct locations, no gamma step pending; ts_hybrid's launch
 // geometry (its per-thread partial sums are the same sums, whatever holds the weights)
-void TSAMD_CAT(launch_hybhol_k, TSAMD_K)(uint32_t grid, uint32_t chunk, hipStream_t stream, const DevParams &p, uint32_t par,
-                                         const uint32_t *sched, uint32_t n, uint32_t serial) {
+static void launch(uint32_t grid, uint32_t chunk, hipStream_t stream, const DevParams &p, uint32_t par, const uint32_t *sched, uint32_t n,
+                   uint32_t serial) {
   // (a sharded context -- ts_hybrid runs on up to 4 ranks: level 2 of the exchanges spans the ranks' group leaders)
   if (p.xchg_world == 0u)
     hipLaunchKernelGGL((ts_hybhol<TSAMD_K, 0>), dim3(grid), dim3(kResidentBlock), 0, stream, p.ctl, p.w, p.npad, chunk, par, sched, n, p.res, serial, p);
@@ -26,15 +21,9 @@ void TSAMD_CAT(launch_hybhol_k, TSAMD_K)(uint32_t grid, uint32_t chunk, hipStrea
     hipLaunchKernelGGL((ts_hybhol<TSAMD_K, 16>), dim3(grid), dim3(kResidentBlock), 0, stream, p.ctl, p.w, p.npad, chunk, par, sched, n, p.res, serial, p);
 }
 
-int TSAMD_CAT(hybhol_blocks_per_cu_k, TSAMD_K)() {
-  int nb = 0, nb2 = 0, nb3 = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ts_hybhol<TSAMD_K, 0>, kResidentBlock, 0) != hipSuccess) nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, ts_hybhol<TSAMD_K, 8>, kResidentBlock, 0) != hipSuccess) nb2 = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb3, ts_hybhol<TSAMD_K, 16>, kResidentBlock, 0) != hipSuccess) nb3 = 0;
-  return nb < nb2 ? (nb < nb3 ? nb : nb3) : (nb2 < nb3 ? nb2 : nb3);
-}
+static int blocks_per_cu() { return min_blocks_per_cu(ts_hybhol<TSAMD_K, 0>, ts_hybhol<TSAMD_K, 8>, ts_hybhol<TSAMD_K, 16>); }
 
-// locations per exchange (what tsamd_holblock_info reports)
-int TSAMD_CAT(hybhol_batch_k, TSAMD_K)() { return hh_batch(TSAMD_K); }
+// (batch: locations per exchange -- what tsamd_holblock_info reports)
+TSAMD_EXPORT_OPS(WholeOps, hybhol, launch, blocks_per_cu, hh_batch(TSAMD_K));
 
 }  // namespace tsamd

@@ -25,18 +25,7 @@
 
 namespace tsamd {
 
-// locations whose accumulators AND exp(Elogbeta) a thread holds at once (4 K BA <= 64 doubles: with the pairs re-read from
-// LDS per item and four locations' accumulators -- round 4's first form -- a sub-batch sweep took twice the instructions) ...
-constexpr int hol_sub(int k) { return k <= 4 ? 4 : k <= 8 ? 2 : 1; }
-// ... and locations per exchange: a multiple of that, at most 16, rows of at most 256 values (BX K <= 128)
-constexpr int hol_batch(int k) {
-  const int ba = hol_sub(k);
-  int n = 128 / (k * ba);
-  if (n > 16 / ba) n = 16 / ba;
-  if (n < 1) n = 1;
-  return n * ba;
-}
-constexpr uint32_t kHolChunk = 1u << 14;
+// hol_sub, hol_batch, kHolChunk: tsamd_capacity.h
 
 template <int KT, int WR>
 __global__ __launch_bounds__(256, 1) void ts_holblock(Ctl *ctl_a, const double *w_a, uint32_t npad_a, uint32_t chunk_a, uint32_t par_arg,

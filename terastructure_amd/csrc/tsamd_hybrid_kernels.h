@@ -20,20 +20,7 @@
 
 namespace tsamd {
 
-// items whose weights live in LDS: what 160 KB hold beside the K x 2 arrays, at most 16 (their codes share one register)
-constexpr int hy_lds_items(int k) {
-  const int n = (160 * 1024 - 1024 - 200 * k) / (k * 8 * 256);
-  return n > 16 ? 16 : n;
-}
-// items in registers: ts_schedule's, one fewer above K = 20 (the streamed items' pipeline needs the registers); round 6, from the
-// build's resource table (profiles/r06_kernel_resources.txt): K = 9 13 instead of 14 and K = 29 ... 32 one instead of two -- the
-// streamed instantiations of those K used 20 ... 236 bytes of scratch
-// (K = 22: floor(112 / 22) - 1 = 4, as before ts_schedule<22> went from 5 items to 4 in round 6)
-constexpr int hy_reg_items(int k) { return k == 9 ? 13 : k <= 20 ? resident_items(k) : k <= 24 ? 112 / k - 1 : k <= 28 ? 2 : 1; }
-// individuals a workgroup holds without streaming any weights
-constexpr int hybrid_resident_capacity(int k) { return (hy_reg_items(k) + hy_lds_items(k)) * kResidentBlock; }
-// streamed items per thread at most (a bound on the loop, not a register budget: 4M individuals per GPU at least)
-constexpr int kHybridMaxStreamed = 64;
+// hy_lds_items, hy_reg_items, hybrid_resident_capacity, kHybridMaxStreamed: tsamd_capacity.h
 
 // update_gamma + update_rho_indiv (src/snpsamplinge.cc:688-719) for one individual with nodekappa = 0.5, then the new
 // weights -- ts_schedule's lean form: (1 - rho) gamma + rho alpha + w_k (c0 sb_k0 + c1 sb_k1), rho * scale folded into

@@ -2,23 +2,17 @@
 // -DTSAMD_K=<k> (terastructure_amd/build.py), so the builds run in parallel and the
 // kernels see K as a compile-time constant.
 #include "tsamd_resident_kernels.h"
-
-#ifndef TSAMD_K
-#error "compile with -DTSAMD_K=<populations>"
-#endif
+#include "tsamd_unit.h"
 
 // leading scalar arguments of ts_pass (kernel-argument preload, tsamd_kernels.h), then the full parameter block
 #define TSAMD_PASS_ARGS(chunk) \
   p.ctl, p.partials, p.w, p.npad, (chunk), par, nrows_hint, (p.xchg_world == 0u && p.rows_from_lt == 0u) ? 1u : 0u, p
 
-#define TSAMD_CAT2(a, b) a##b
-#define TSAMD_CAT(a, b) TSAMD_CAT2(a, b)
-
 namespace tsamd {
 
 // (kLaunchResident: `block` carries the chunk -- items per workgroup -- and `serial` the host's launch serial)
-void TSAMD_CAT(launch_k, TSAMD_K)(int which, uint32_t grid, uint32_t block, hipStream_t stream, const DevParams &p,
-                                  uint32_t par, uint32_t nrows_hint, uint32_t serial) {
+static void launch(int which, uint32_t grid, uint32_t block, hipStream_t stream, const DevParams &p, uint32_t par, uint32_t nrows_hint,
+                   uint32_t serial) {
   constexpr int K = TSAMD_K;
   switch (which) {
     case kLaunchPass:
@@ -47,7 +41,7 @@ void TSAMD_CAT(launch_k, TSAMD_K)(int which, uint32_t grid, uint32_t block, hipS
 }
 
 // can a workgroup of the resident plain-pass kernel run on a compute unit (register budget)?
-int TSAMD_CAT(resident_blocks_per_cu_k, TSAMD_K)() {
+static int resident_blocks_per_cu() {
   constexpr int K = TSAMD_K;
   if constexpr (K <= kResidentMaxK) {
     int nb = 0;
@@ -58,12 +52,14 @@ int TSAMD_CAT(resident_blocks_per_cu_k, TSAMD_K)() {
 }
 
 // resident first-pass workgroups per compute unit (register-bound: 2 at K = 8, 1 from K = 12)
-int TSAMD_CAT(first_blocks_per_cu_k, TSAMD_K)(int vec) {
+static int first_blocks_per_cu(int vec) {
   constexpr int K = TSAMD_K;
   int nb = 0;
   const hipError_t e = vec == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ts_pass<K, true, 256, 2>, 256, 0)
                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ts_pass<K, true, 256, 1>, 256, 0);
   return e == hipSuccess ? nb : 0;
 }
+
+TSAMD_EXPORT_OPS(PassOps, pass, launch, first_blocks_per_cu, resident_blocks_per_cu);
 
 }  // namespace tsamd

@@ -1009,7 +1009,7 @@ __global__ __launch_bounds__(kBlock) void ts_refresh_w(DevParams p) {
 }
 
 // Host-side launcher of the K-specialised kernels; one translation unit per K
-// (tsamd_inst.hip compiled with -DTSAMD_K=<k>) defines tsamd::launch_k<k>.
+// (tsamd_inst.hip compiled with -DTSAMD_K=<k>) exports one in its tsamd::pass_ops_k<k> (tsamd_unit.h).
 enum LaunchWhich { kLaunchPass = 0, kLaunchFirst = 1, kLaunchRefresh = 2, kLaunchResident = 3 };
 using LaunchFn = void (*)(int which, uint32_t grid, uint32_t block, hipStream_t stream, const DevParams &p,
                           uint32_t par, uint32_t nrows_hint, uint32_t serial);

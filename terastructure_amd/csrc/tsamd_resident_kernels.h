@@ -31,23 +31,7 @@ namespace tsamd {
 #endif
 
 // ---- geometry per K ---------------------------------------------------------------------------------------------
-constexpr int kResidentMaxK = 32;
-constexpr int kResidentBlock = 256;
-#ifdef TSAMD_RES_VEC  // (experiments, UNIT=all tools/variant.sh: 2 = pairs of individuals per item at K <= 8, round 2's geometry)
-constexpr int resident_vec(int k) { return k <= 8 ? TSAMD_RES_VEC : 1; }
-#else
-constexpr int resident_vec(int) { return 1; }
-#endif
-// (K = 22: 4, not floor(112 / 22) = 5 -- with 110 doubles of weights every ts_schedule<22> instantiation spilled 36 ... 76 bytes
-// to scratch: profiles/r06_kernel_resources.txt, round 6)
-constexpr int resident_items(int k) { return k <= 8 ? 16 / resident_vec(k) : k <= 16 ? 128 / k : k == 22 ? 4 : k <= 24 ? 112 / k : 3; }
-// individuals a workgroup can hold
-constexpr int resident_capacity(int k) { return resident_items(k) * resident_vec(k) * kResidentBlock; }
-// ... and what a thread of a SHARDED launch holds (ts_schedule<K, ., WR > 0>, ts_holblock<K, WR > 0>: the ranks' launches share one
-// geometry rule, resident_geometry in csrc/tsamd.hip): K = 16 one item less -- its 128 doubles of weights fill the AGPR half of the
-// register file, and the sharded exchange's few extra registers went to scratch (20 ... 52 bytes); K = 14 (9 x 14 = 126 doubles) likewise
-constexpr int sharded_items(int k) { return k == 16 ? 7 : k == 14 ? 8 : resident_items(k); }
-constexpr int sched_items(int k, int wr) { return wr > 0 ? sharded_items(k) : resident_items(k); }
+// kResidentMaxK, kResidentBlock, resident_vec / _items / _capacity, sharded_items, sched_items: tsamd_capacity.h
 
 // ---- in-launch exchange -----------------------------------------------------------------------------------------
 // Per pass every workgroup contributes its partial row (2K doubles) and every workgroup gets the fixed-order total,
@@ -67,12 +51,7 @@ constexpr int sched_items(int k, int wr) { return wr > 0 ? sharded_items(k) : re
 // tag = a counter in Ctl (xseq) that never repeats, so nothing is re-initialised between launches.  Every wait is
 // bounded; a failure sets abort_word, which ends all later waits at once and turns every later kernel of the context
 // into a no-op until the host has dealt with it (tsamd_synchronize).
-constexpr int kResGroups = 8;    // (Xchg::res_sums is laid out for these two)
-constexpr int kResMembers = 32;  // workgroups per group (grid <= 256)
-#ifndef TSAMD_ONE_LEVEL  // (experiments: 0 = always two levels.  Measured at K = 8: up to 16 rows 34.5 us per update against
-#define TSAMD_ONE_LEVEL 32  // 43.8 with two levels; 17 ... 32 rows -- since the row sums run on the vector ALU -- 33.8 against
-#endif                      // 37.1 at N = 16 000; 64 loses at every size: profiles/r03_experiments.md)
-constexpr int kResOneLevelGrid = TSAMD_ONE_LEVEL;  // up to this many workgroups (one GPU) the exchange has ONE level: everybody reads every row
+// (kResGroups = 8 groups of kResMembers = 32 workgroups, kResOneLevelGrid: tsamd_capacity.h)
 constexpr int res_blocks(int k) { return (4 * k + 31) / 32; }  // 32-granule column blocks of a row of 2K values
 constexpr int kResMaxGran = 32 * res_blocks(kResidentMaxK);
 constexpr int kResRegionRows = kResGroups * kResMembers + 2 * kResGroups;  // member rows, then two slots of group sums

@@ -3,12 +3,7 @@
 // is one loop over the schedule around fully unrolled sweeps, and loop-invariant code motion would hoist
 // a few hundred addresses and constants out of that loop into registers the kernel needs for the weights.
 #include "tsamd_resident_kernels.h"
-
-#ifndef TSAMD_K
-#error "compile with -DTSAMD_K=<populations>"
-#endif
-#define TSAMD_CAT2(a, b) a##b
-#define TSAMD_CAT(a, b) TSAMD_CAT2(a, b)
+#include "tsamd_unit.h"
 
 namespace tsamd {
 
@@ -30,8 +25,8 @@ static_assert(sizeof(((Xchg *)nullptr)->res_sums) / sizeof(unsigned long long) >
 #define TSAMD_SCHED_LAUNCH(PARTIAL, WR)                                                                                               \
   hipLaunchKernelGGL((ts_schedule<TSAMD_K, (PARTIAL) || kAlwaysPartial, WR>), dim3(grid), dim3(kResidentBlock), 0, stream, p.ctl, p.w, p.npad, \
                      chunk, par, sched, n, p.res, serial, p)
-void TSAMD_CAT(launch_schedule_k, TSAMD_K)(uint32_t grid, uint32_t chunk, hipStream_t stream, const DevParams &p, uint32_t par,
-                                           const uint32_t *sched, uint32_t n, uint32_t serial) {
+static void launch(uint32_t grid, uint32_t chunk, hipStream_t stream, const DevParams &p, uint32_t par, const uint32_t *sched, uint32_t n,
+                   uint32_t serial) {
   // (K > 8: always the instantiation with the skip branches -- without them the scheduler moves the items' loads so far
   // ahead that the kernel no longer fits the register file)
   const bool partial = kAlwaysPartial || chunk <= (uint32_t)((resident_items(TSAMD_K) - 1) * kResidentBlock);
@@ -47,23 +42,12 @@ void TSAMD_CAT(launch_schedule_k, TSAMD_K)(uint32_t grid, uint32_t chunk, hipStr
   }
 }
 
-// does a workgroup of it fit a compute unit (register budget)?  (worst case of the instantiations)
-int TSAMD_CAT(schedule_blocks_per_cu_k, TSAMD_K)() {
-  int worst = 1 << 30;
-  auto probe = [&](auto kernel) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kResidentBlock, 0) != hipSuccess) nb = 0;
-    worst = nb < worst ? nb : worst;
-  };
-  probe(ts_schedule<TSAMD_K, kAlwaysPartial, 0>);
-  probe(ts_schedule<TSAMD_K, true, 0>);
-  probe(ts_schedule<TSAMD_K, kAlwaysPartial, 8>);
-  probe(ts_schedule<TSAMD_K, true, 8>);
-  probe(ts_schedule<TSAMD_K, kAlwaysPartial, 16>);
-  probe(ts_schedule<TSAMD_K, true, 16>);
-  probe(ts_schedule<TSAMD_K, kAlwaysPartial, 32>);
-  probe(ts_schedule<TSAMD_K, true, 32>);
-  return worst;
+static int blocks_per_cu() {
+  return min_blocks_per_cu(ts_schedule<TSAMD_K, kAlwaysPartial, 0>, ts_schedule<TSAMD_K, true, 0>, ts_schedule<TSAMD_K, kAlwaysPartial, 8>,
+                           ts_schedule<TSAMD_K, true, 8>, ts_schedule<TSAMD_K, kAlwaysPartial, 16>, ts_schedule<TSAMD_K, true, 16>,
+                           ts_schedule<TSAMD_K, kAlwaysPartial, 32>, ts_schedule<TSAMD_K, true, 32>);
 }
+
+TSAMD_EXPORT_OPS(WholeOps, schedule, launch, blocks_per_cu, 0);
 
 }  // namespace tsamd

@@ -10,8 +10,7 @@
 
 namespace tsamd {
 
-constexpr int kWideBlock = 512;
-constexpr int kWideItems = 8;   // max individuals per thread (the launch geometry guarantees it)
+// (kWideBlock, kWideItems: tsamd_capacity.h)
 constexpr int kWideChunk = 8;   // populations accumulated per register chunk
 constexpr int kWideJ = 2 * TSAMD_MAX_K;
 

@@ -1,5 +1,5 @@
-"""The launch geometries of the resident kernels that small and mid-sized shards take (resident_geometry in
-csrc/tsamd.hip), each against the CPU oracle in every launch mode the context qualifies for:
+"""The launch geometries of the resident kernels that small and mid-sized shards take (plan_launch in
+csrc/tsamd_plan.h), each against the CPU oracle in every launch mode the context qualifies for:
 
   * the SHRUNK grid: a shard that would fill 33 ... 80 workgroups with one individual per thread is launched on <= 32
     workgroups with two or three per thread, so that its in-launch exchange has ONE level; at K <= 8 every wave then runs

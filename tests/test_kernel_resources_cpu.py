@@ -20,7 +20,7 @@ def rows():
 
 
 def test_no_whole_launch_kernel_the_launchers_can_select_uses_scratch(rows):
-    """every instantiation launch_schedule_k / launch_holblock_k / launch_hybrid_k / launch_hybhol_k can select
+    """every instantiation the launchers of tsamd_sched.hip / tsamd_hol.hip / tsamd_hyb.hip / tsamd_hhol.hip can select
     (csrc/tsamd_sched.hip, tsamd_hol.hip, tsamd_hyb.hip, tsamd_hhol.hip): K = 1 ... 32, every PARTIAL / WR / STREAM form"""
     fams = ("ts_schedule<", "ts_holblock<", "ts_hybrid<", "ts_hybhol<")
     sel = [r for r in rows if r["name"].startswith(fams)]
@@ -45,7 +45,7 @@ def test_known_scratch_users_are_exactly_the_documented_ones(rows):
     for r in rows:
         if r["name"].startswith("ts_resident<"):
             assert r["private_segment_fixed_size"] <= 36, r
-    # the launch-per-pass kernels the default geometry runs (configure_launch, csrc/tsamd.hip): first pass ts_pass<K, true, 256, 1>,
+    # the launch-per-pass kernels the default geometry runs (plan_launch, csrc/tsamd_plan.h): first pass ts_pass<K, true, 256, 1>,
     # plain pass ts_pass<K, false, 512, 2> up to K = 16 and <K, false, 256, 2> above -- scratch-free up to K = 22 (first pass) / 29
     for r in rows:
         m = re.match(r"ts_pass<(\d+), (true|false), (\d+), (\d+)>", r["name"])
