@@ -153,6 +153,8 @@ struct Timing {
   double ckpt_blocking = 0, ckpt_first = 0, resume = 0;  // of save_blocking: exporting the engine state for checkpoint.bin; reading and importing one
   uint64_t ckpt_bytes = 0;
   uint32_t reports = 0, saves = 0, ckpts = 0;
+  double logl = 0;  // -logl: evaluating the training likelihood and writing its files
+  uint32_t logls = 0;
 };
 
 struct Run {
@@ -319,6 +321,9 @@ void usage() {
           "\t-rfreq <val>\t checks for convergence and logs output every <val> iterations\n"
           "\t-seed <val>\t random seed\n"
           "\t-compute-beta\t compute allele frequencies given ./gamma.txt\n"
+          "\t-logl\t\t with every report, the log-likelihood of the training data: a line in likelihood-analysis.txt\n"
+          "\t\t\t (validation.txt's format); at the end logl_snp.txt (loc, count, mean) and logl_indiv.txt\n"
+          "\t\t\t (count, mean; theta.txt's order)\n"
           "\t-device <id>\t HIP device ordinal (default 0)\n"
           "\t-devices <a,b,..>\t shard the individuals over these HIP devices (one shard each)\n"
           "\t-ingest-threads <T>\t reader threads of the .bed ingest (default: up to 8)\n"
@@ -792,6 +797,7 @@ void write_timing(Run &r) {
     fprintf(f, "checkpoint, main thread blocked (part of save_model's): %.3f (%u checkpoints, %.1f MB of engine state each; the first, which pins its buffers: %.3f)\n",
             t.ckpt_blocking, t.ckpts, t.ckpts ? (double)t.ckpt_bytes / t.ckpts / 1e6 : 0.0, t.ckpt_first);
   if (!r.o.resume.empty()) fprintf(f, "resume (read, validate, import): %.3f\n", t.resume);
+  if (r.o.logl) fprintf(f, "training likelihood (-logl): %.3f (%u evaluations)\n", t.logl, t.logls);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
@@ -842,6 +848,63 @@ bool compute_likelihood(Run &r, bool first) {
   }
   r.prev_h = a;
   return stop;
+}
+
+// -logl: the log-likelihood of the training data under the current state (tsamd_train_loglik: every stored entry of all l
+// columns on every shard; held-out entries are not training data).  What the reference announces ("+ computing initial
+// training likelihood", the likelihood-analysis.txt it unlinks, src/snpsamplinge.cc:533-534 commented out) and never
+// computes.  Every report appends "iter \t secs \t mean \t count \t exp(mean)" to likelihood-analysis.txt; with the final
+// save_model (per_entry) the call writes logl_snp.txt ("loc \t count \t mean") and logl_indiv.txt ("count \t mean", theta.txt's
+// order) instead.
+void train_likelihood(Run &r, bool per_entry) {
+  Stopwatch sw;
+  const uint32_t l = r.o.l, n = r.o.n;
+  std::vector<double> loc_sum, indiv_sum, ls;
+  std::vector<uint64_t> loc_cnt;
+  std::vector<uint32_t> indiv_cnt, lc;
+  if (per_entry) {
+    loc_sum.assign(l, 0.0), loc_cnt.assign(l, 0), ls.resize(l), lc.resize(l);
+    indiv_sum.assign(n, 0.0), indiv_cnt.assign(n, 0);
+  }
+  double total = 0.0;
+  uint64_t count = 0;
+  for (size_t i = 0; i < r.ctxs.size(); ++i) {  // shard after shard; no exchange is involved
+    uint32_t b, c;
+    shard_span(r, i, b, c);
+    double s = 0.0;
+    uint64_t m = 0;
+    r.ctx = r.ctxs[i];
+    TS(r, tsamd_train_loglik(r.ctxs[i], nullptr, l, per_entry ? ls.data() : nullptr, per_entry ? lc.data() : nullptr,
+                             per_entry ? indiv_sum.data() + b : nullptr, per_entry ? indiv_cnt.data() + b : nullptr, &s, &m));
+    total += s;
+    count += m;
+    if (per_entry)
+      for (uint32_t j = 0; j < l; ++j) loc_sum[j] += ls[j], loc_cnt[j] += lc[j];
+  }
+  r.ctx = r.ctxs[0];
+  if (!per_entry) {
+    const double mean = count ? total / (double)count : 0.0;
+    FILE *f = fopen(r.file_str("/likelihood-analysis.txt").c_str(), "a");
+    if (!f) {
+      r.lerr("cannot open likelihood-analysis.txt:%s\n", strerror(errno));
+      exit(-1);
+    }
+    fprintf(f, "%d\t%d\t%.9f\t%llu\t%f\n", r.iter, r.duration(), mean, (unsigned long long)count, exp(mean));
+    fclose(f);
+  } else {
+    FILE *fs = fopen(r.file_str("/logl_snp.txt").c_str(), "w"), *fi = fopen(r.file_str("/logl_indiv.txt").c_str(), "w");
+    if (!fs || !fi) {
+      r.lerr("cannot open logl_snp.txt / logl_indiv.txt:%s\n", strerror(errno));
+      exit(-1);
+    }
+    for (uint32_t j = 0; j < l; ++j)
+      fprintf(fs, "%u\t%llu\t%.8f\n", j, (unsigned long long)loc_cnt[j], loc_cnt[j] ? loc_sum[j] / (double)loc_cnt[j] : 0.0);
+    for (uint32_t i = 0; i < n; ++i) fprintf(fi, "%u\t%.8f\n", indiv_cnt[i], indiv_cnt[i] ? indiv_sum[i] / (double)indiv_cnt[i] : 0.0);
+    fclose(fs);
+    fclose(fi);
+  }
+  r.tm.logl += sw.lap();
+  r.tm.logls++;
 }
 
 void save_beta(Run &r, const std::vector<uint32_t> *locs) {
@@ -1237,6 +1300,7 @@ int main(int argc, char **argv) {
     compute_likelihood(r, true);
     r.tm.report += phase.lap();
     r.tm.reports++;
+    if (o.logl) train_likelihood(r, false);
     save_model(r, false);  // (the initial state: nothing to resume from yet)
   }
   printf("\n+ computing initial training likelihood\n+ done..\n+ initialization end\n");
@@ -1264,6 +1328,7 @@ int main(int argc, char **argv) {
       const bool stop = compute_likelihood(r, false);
       r.tm.report += phase.lap();
       r.tm.reports++;
+      if (o.logl) train_likelihood(r, false);
       if (stop) {
         save_model(r);
         break;
@@ -1279,6 +1344,7 @@ int main(int argc, char **argv) {
     }
   }
   printf("\n");
+  if (o.logl) train_likelihood(r, true);  // the state of the final save_model: the per-location and per-individual files
   finish_saves(r);  // gamma.txt / theta.txt complete and closed before the process ends
   write_timing(r);
   destroy_all(r);

@@ -66,7 +66,9 @@ typedef struct tsamd_config {
 #define TSAMD_FLAG_NO_GRAPH 2u       /* tsamd_run_schedule launches eagerly instead of replaying a hipGraph */
 #define TSAMD_FLAG_TEST_HOOKS 4u     /* honour the TSAMD_TEST_* environment hooks (tests only): those of the peer-to-peer exchange, and
                                         TSAMD_TEST_MAX_WORKGROUPS (the resident kernels' launch geometry as on a device with that
-                                        many compute units: small shards then run the many-items-per-thread paths) */
+                                        many compute units: small shards then run the many-items-per-thread paths; for
+                                        tsamd_train_loglik, its segment count) and TSAMD_TEST_LOGLIK_CHUNK (locations per
+                                        internal chunk of tsamd_train_loglik) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -184,6 +186,19 @@ int tsamd_heldout_loglik(tsamd_ctx *ctx, uint32_t loc, double *sum, uint32_t *co
  * sum / count = their totals added in the listed order. */
 int tsamd_heldout_eval(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n, int run_updates, double *loc_sums,
                        uint32_t *loc_counts, double *sum, uint32_t *count);
+/* Training-data log-likelihood of the current state; changes no state.  The term of tsamd_heldout_loglik,
+ * log(max(C(2,y) q^y (1-q)^(2-y), 1e-30)) with q = sum_k Ebeta[loc][k] * Etheta[n][k] (the values tsamd_get_ebeta and
+ * tsamd_get_theta return at that moment: a pending gamma step stays pending), for every individual of the shard whose
+ * stored code at loc is not 01 (missing, held out by tsamd_set_heldout, padding), in ONE sweep of the listed columns
+ * (csrc/tsamd_loglik_kernels.h).  locs == NULL means locations 0 .. n_locs-1 (n_locs <= l); a repeated location is
+ * evaluated and counted again.  loc_sums / loc_counts [n_locs] and indiv_sums / indiv_counts [shard_count] may be NULL;
+ * sum / count (may be NULL) = the totals of the per-location values added in the listed order.  No atomics, a fixed
+ * summation order: results are bitwise reproducible, and a location's sum depends neither on the other locations of the
+ * call nor on how the library cuts the list into chunks.  Synchronous; settles the context first like every getter.
+ * TSAMD_EINVAL for a location >= l or n_locs == 0; every k the context accepts is served.  On a sharded context every
+ * rank answers for its own shard and the caller adds the ranks' results: no exchange is involved. */
+int tsamd_train_loglik(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, double *loc_sums, uint32_t *loc_counts,
+                       double *indiv_sums, uint32_t *indiv_counts, double *sum, uint64_t *count);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

@@ -69,6 +69,7 @@ SYMBOLS = {
     "tsamd_clear_pending": (_int, [_vp]),
     "tsamd_heldout_loglik": (_int, [_vp, _u32, _pd, _pu32]),
     "tsamd_heldout_eval": (_int, [_vp, _pu32, _u32, _int, _pd, _pu32, _pd, _pu32]),
+    "tsamd_train_loglik": (_int, [_vp, _pu32, _u32, _pd, _pu32, _pd, _pu32, _pd, _pu64]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

@@ -71,6 +71,8 @@ def _units():
     for k in range(1, SCHED_MAX_K + 1):
         units.append((os.path.join(OBJ_DIR, f"hhol_k{k}.o"), os.path.join(CSRC, "tsamd_hhol.hip"),
                       [f"-DTSAMD_K={k}", "-mllvm", "-disable-machine-licm"]))
+    # tsamd_train_loglik's kernels, every K in one unit (csrc/tsamd_loglik.hip)
+    units.append((os.path.join(OBJ_DIR, "loglik.o"), os.path.join(CSRC, "tsamd_loglik.hip"), []))
     return units
 
 

@@ -24,6 +24,7 @@
 #include "tsamd_hybrid_kernels.h"
 #include "tsamd_wide_kernels.h"
 #include "tsamd_plan.h"
+#include "tsamd_loglik_plan.h"
 #include "tsamd_unit.h"
 
 using namespace tsamd;
@@ -116,6 +117,14 @@ struct tsamd_ctx {
   HeldReq *d_hreq = nullptr;
   double *d_hsums = nullptr;
   size_t hreq_cap = 0;
+  // tsamd_train_loglik: partial-sum buffers (loglik_geometry: at most kLoglikScratchBound bytes), the chunk's locations and results, the
+  // call's per-individual accumulators and, at k > TSAMD_SPECIALIZED_K, the normalised theta; allocated on first use
+  void *d_ll_part = nullptr;
+  size_t ll_part_bytes = 0;
+  void *d_ll_chunk = nullptr;  // [chunk] locations, sums, counts
+  size_t ll_chunk_cap = 0;
+  void *d_ll_acc = nullptr;    // [npad] sums, [npad] counts
+  double *d_ll_thn = nullptr;  // [k][npad]
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -597,6 +606,10 @@ void tsamd_destroy(tsamd_ctx *c) {
   hipFree(c->d_fold_ids);
   hipFree(c->d_fold_orig);
   hipFree(c->d_hsums);
+  hipFree(c->d_ll_part);
+  hipFree(c->d_ll_chunk);
+  hipFree(c->d_ll_acc);
+  hipFree(c->d_ll_thn);
   if (c->h_stage) hipHostFree(c->h_stage);
   hipFree(c->d_state);
   for (auto &j : c->journal) {
@@ -1616,6 +1629,85 @@ int tsamd_heldout_eval(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int run_u
 
 int tsamd_heldout_loglik(tsamd_ctx *c, uint32_t loc, double *sum, uint32_t *count) {
   return tsamd_heldout_eval(c, &loc, 1, 0, nullptr, nullptr, sum, count);
+}
+
+// One sweep of the listed columns (csrc/tsamd_loglik_kernels.h), chunk after chunk; reads the state only.
+int tsamd_train_loglik(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, double *loc_sums, uint32_t *loc_counts, double *indiv_sums,
+                       uint32_t *indiv_counts, double *sum, uint64_t *count) {
+  CHECK_CTX(c);
+  if (sum) *sum = 0.0;
+  if (count) *count = 0;
+  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
+  if (locs)
+    for (uint32_t i = 0; i < n_locs; ++i)
+      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
+  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
+  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
+  const uint32_t K = c->cfg.k, np = c->npad;
+  const LoglikGeom g = loglik_geometry(np, K, cus, hooks ? env_u32("TSAMD_TEST_LOGLIK_CHUNK", 0) : 0u);
+  const uint32_t chunk = std::min(g.chunk, n_locs);
+
+  const size_t part_loc = (size_t)chunk * g.ntiles, part_ind = (size_t)g.nseg_max * np;
+  const size_t part_bytes = (part_loc + part_ind) * kLoglikPartBytes;
+  if (part_bytes > c->ll_part_bytes) {
+    hipFree(c->d_ll_part);
+    c->d_ll_part = nullptr, c->ll_part_bytes = 0;
+    HIP_TRY(c, hipMalloc(&c->d_ll_part, part_bytes));
+    c->ll_part_bytes = part_bytes;
+  }
+  if (chunk > c->ll_chunk_cap) {
+    hipFree(c->d_ll_chunk);
+    c->d_ll_chunk = nullptr, c->ll_chunk_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->d_ll_chunk, (size_t)chunk * 16));
+    c->ll_chunk_cap = chunk;
+  }
+  if (!c->d_ll_acc) HIP_TRY(c, hipMalloc(&c->d_ll_acc, (size_t)np * kLoglikPartBytes));
+  if (K > (uint32_t)TSAMD_SPECIALIZED_K && !c->d_ll_thn) HIP_TRY(c, hipMalloc((void **)&c->d_ll_thn, (size_t)K * np * sizeof(double)));
+  // (the doubles first: every array starts on a multiple of 8 bytes)
+  double *part_loc_sum = (double *)c->d_ll_part, *part_ind_sum = part_loc_sum + part_loc;
+  uint32_t *part_loc_cnt = (uint32_t *)(part_ind_sum + part_ind), *part_ind_cnt = part_loc_cnt + part_loc;
+  double *d_sum = (double *)c->d_ll_chunk;
+  uint32_t *d_cnt = (uint32_t *)(d_sum + c->ll_chunk_cap), *d_locs = d_cnt + c->ll_chunk_cap;
+  double *acc_sum = (double *)c->d_ll_acc;
+  uint32_t *acc_cnt = (uint32_t *)(acc_sum + np);
+
+  HIP_TRY(c, hipMemsetAsync(c->d_ll_acc, 0, (size_t)np * kLoglikPartBytes, c->stream));
+  if (c->d_ll_thn) loglik_launch_theta(c->p.gam, np, K, c->d_ll_thn, c->stream);
+  std::vector<uint32_t> h_locs(chunk), h_cnt(chunk);
+  std::vector<double> h_sum(chunk);
+  double total = 0.0;
+  uint64_t total_cnt = 0;
+  for (uint32_t off = 0; off < n_locs; off += chunk) {
+    const uint32_t len = std::min(chunk, n_locs - off);
+    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
+    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const LoglikSegs sg = loglik_segments(g, len);
+    LoglikArgs a{};
+    a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.thn = c->d_ll_thn, a.lam = c->p.lam, a.locs = d_locs;
+    a.npad = np, a.K = K, a.len = len, a.seg_len = sg.seg_len, a.ntiles = g.ntiles;
+    a.part_loc_sum = part_loc_sum, a.part_loc_cnt = part_loc_cnt, a.part_ind_sum = part_ind_sum, a.part_ind_cnt = part_ind_cnt;
+    loglik_launch_chunk(a, sg.nseg, d_sum, d_cnt, acc_sum, acc_cnt, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(h_sum.data(), d_sum, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < len; ++i) {  // listed order
+      if (loc_sums) loc_sums[off + i] = h_sum[i];
+      if (loc_counts) loc_counts[off + i] = h_cnt[i];
+      total += h_sum[i];
+      total_cnt += h_cnt[i];
+    }
+  }
+  if (indiv_sums) HIP_TRY(c, hipMemcpyAsync(indiv_sums, acc_sum, (size_t)c->n_local * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (indiv_counts) HIP_TRY(c, hipMemcpyAsync(indiv_counts, acc_cnt, (size_t)c->n_local * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (sum) *sum = total;
+  if (count) *count = total_cnt;
+  return TSAMD_OK;
 }
 
 int tsamd_comm_unique_id(uint8_t id[TSAMD_COMM_ID_BYTES]) {

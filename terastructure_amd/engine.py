@@ -230,6 +230,31 @@ class Engine:
                                               C.byref(s), C.byref(c)))
         return s.value, c.value, sums, cnts
 
+    def train_loglik(self, locs=None, per_loc=True, per_indiv=True):
+        """training-data log-likelihood of the current state over locs (None: every location) -- tsamd_train_loglik:
+        dict(sum, count[, loc_sums, loc_counts][, indiv_sums, indiv_counts]); the per-individual arrays cover this
+        engine's shard.  Changes no state."""
+        if locs is None:
+            a, n_locs = None, self.l
+        else:
+            a = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = a.size
+        ls = np.zeros(n_locs, dtype=np.float64) if per_loc else None
+        lc = np.zeros(n_locs, dtype=np.uint32) if per_loc else None
+        ns = np.zeros(self.shard_count, dtype=np.float64) if per_indiv else None
+        nc = np.zeros(self.shard_count, dtype=np.uint32) if per_indiv else None
+        s, c = C.c_double(0), C.c_uint64(0)
+        self._check(self.h.tsamd_train_loglik(self.ctx, None if a is None else _up(a), n_locs,
+                                              None if ls is None else _dp(ls), None if lc is None else _up(lc),
+                                              None if ns is None else _dp(ns), None if nc is None else _up(nc),
+                                              C.byref(s), C.byref(c)))
+        out = dict(sum=s.value, count=c.value)
+        if per_loc:
+            out.update(loc_sums=ls, loc_counts=lc)
+        if per_indiv:
+            out.update(indiv_sums=ns, indiv_counts=nc)
+        return out
+
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
         """(indiv_bytes, loc_bytes) of the two state blobs -- tsamd_state_sizes"""
