@@ -297,4 +297,41 @@ inline bool read_file(const std::string &path, const Expect &want, FileHeader *f
   return true;
 }
 
+// -project: the location part of a checkpoint, for a cohort of another size.  The same magic / version / checksum checks
+// as read_file; l and k must be the file's, while n, the seed and rfreq are the training run's own business.  The individual
+// part is not read (its bytes are counted: a truncated file is refused).  lambda [l][k][2] is the first array of the
+// location part's payload (include/tsamd.h).
+inline bool read_loc_part(const std::string &path, uint32_t l, uint32_t k, FileHeader *fh, Buf *loc, std::string *err) {
+  FILE *f = fopen(path.c_str(), "rb");
+  if (!f) return *err = "cannot open " + path + ": " + strerror(errno), false;
+  auto bad = [&](const std::string &why) {
+    fclose(f);
+    *err = path + ": " + why;
+    return false;
+  };
+  HostState hs;
+  if (fread(fh, sizeof *fh, 1, f) != 1) return bad("truncated (no file header)");
+  if (fh->magic != kFileMagic) return bad("not a checkpoint file (bad magic)");
+  if (fh->version != kFileVersion) return bad("checkpoint format version " + std::to_string(fh->version) + " is not " + std::to_string(kFileVersion));
+  if (fread(&hs, sizeof hs, 1, f) != 1) return bad("truncated (host state)");
+  if (head_checksum(*fh, hs) != fh->head_checksum) return bad("corrupt (checksum of the file header and the host state)");
+  if (fh->l != l) return bad("written with -l " + std::to_string(fh->l) + ", this run has -l " + std::to_string(l));
+  if (fh->k != k) return bad("written with -k " + std::to_string(fh->k) + ", this run has -k " + std::to_string(k));
+  if (fseeko(f, 0, SEEK_END) != 0) return bad("cannot seek");
+  const uint64_t size = (uint64_t)ftello(f), need = sizeof *fh + sizeof hs + fh->loc_bytes + fh->indiv_bytes;
+  if (fh->loc_bytes > (1ull << 46) || fh->indiv_bytes > (1ull << 46) || size != need)
+    return bad("truncated or corrupt: " + std::to_string(size) + " bytes, its header says " + std::to_string(need));
+  if (fseeko(f, (off_t)(sizeof *fh + sizeof hs), SEEK_SET) != 0) return bad("cannot seek");
+  loc->alloc(fh->loc_bytes);
+  if (fread(loc->data(), 1, fh->loc_bytes, f) != fh->loc_bytes) return bad("truncated (engine state)");
+  fclose(f);
+  f = nullptr;
+  BlobHeader bl;
+  std::string why;
+  if (!check_blob(loc->data(), loc->size(), kPartLoc, "loc", &bl, &why)) return *err = path + ": corrupt: " + why, false;
+  if (bl.n != fh->n || bl.l != fh->l || bl.k != fh->k) return *err = path + ": corrupt: the location part does not belong to the file header", false;
+  if (bl.payload_bytes < 16ull * bl.l * bl.k) return *err = path + ": corrupt: the location part is shorter than its lambda", false;
+  return true;
+}
+
 }  // namespace ckpt

@@ -146,6 +146,9 @@ struct Options {
   bool ingest_only = false;     // extension: read the genotypes into HBM, write param.txt, stop (ingest measurement)
   bool checkpoint = false;      // extension: every save_model after the initial one also writes <run dir>/checkpoint.bin
   std::string resume;           // extension: start from this checkpoint.bin instead of init_gamma
+  std::string project;          // extension: fit this cohort's theta against the lambda of this checkpoint.bin, held fixed
+  uint32_t project_iters = 100; // -project: updates per individual, at most
+  double project_tol = 1e-5;    // -project: an individual stops when its update changes gamma by less (relative mean change)
 };
 
 struct Timing {
@@ -153,6 +156,8 @@ struct Timing {
   double ckpt_blocking = 0, ckpt_first = 0, resume = 0;  // of save_blocking: exporting the engine state for checkpoint.bin; reading and importing one
   uint64_t ckpt_bytes = 0;
   uint32_t reports = 0, saves = 0, ckpts = 0;
+  double project = 0;  // -project: loading the lambda, the fold-in, foldin.txt
+  uint32_t project_iters_run = 0, project_converged = 0;
   double logl = 0;  // -logl: evaluating the training likelihood and writing its files
   uint32_t logls = 0;
 };
@@ -332,7 +337,13 @@ void usage() {
           "\t\t\t the full engine and sampler state of that iteration\n"
           "\t-resume <file>\t continue the run that wrote this checkpoint.bin (same -n -l -k -seed -rfreq and data; any\n"
           "\t\t\t -devices); with the same device count the continuation is bit for bit the uninterrupted\n"
-          "\t\t\t run's.  Not together with -compute-beta\n");
+          "\t\t\t run's.  Not together with -compute-beta\n"
+          "\t-project <file>\t fit the theta of the individuals in -file against the lambda of this checkpoint.bin, held fixed:\n"
+          "\t\t\t -n is THIS cohort's size, -l and -k must be the file's.  Writes theta.txt / gamma.txt and foldin.txt\n"
+          "\t\t\t (individual, updates, last change).  Not together with -resume or -compute-beta\n"
+          "\t-project-iters <I>\t -project: at most this many updates per individual (default 100)\n"
+          "\t-project-tol <t>\t -project: an individual stops once an update changes its gamma by less than this\n"
+          "\t\t\t (mean |change| / mean gamma; default 1e-5; 0: always -project-iters updates)\n");
   fflush(stdout);
 }
 
@@ -401,6 +412,11 @@ void setup_run_dir(Run &r) {
   r.plog_d("stop_threshold", o.stop_threshold);
   r.plog_b("checkpoint", o.checkpoint);
   fprintf(r.plog, "resume: %s\n", o.resume.empty() ? "False" : o.resume.c_str()), fflush(r.plog);
+  if (!o.project.empty()) {  // (a line of its own only in a -project run: param.txt of every other run is unchanged)
+    fprintf(r.plog, "project: %s\n", o.project.c_str());
+    r.plog_u("project_iters", o.project_iters);
+    fprintf(r.plog, "project_tol: %.9g\n", o.project_tol), fflush(r.plog);
+  }
   const std::string nd = r.file_str("/network.dat");
   unlink(nd.c_str());
   if (symlink(o.datfname.c_str(), nd.c_str()) < 0) fprintf(stderr, "warning: cannot symlink %s\n", nd.c_str());
@@ -797,9 +813,55 @@ void write_timing(Run &r) {
     fprintf(f, "checkpoint, main thread blocked (part of save_model's): %.3f (%u checkpoints, %.1f MB of engine state each; the first, which pins its buffers: %.3f)\n",
             t.ckpt_blocking, t.ckpts, t.ckpts ? (double)t.ckpt_bytes / t.ckpts / 1e6 : 0.0, t.ckpt_first);
   if (!r.o.resume.empty()) fprintf(f, "resume (read, validate, import): %.3f\n", t.resume);
+  if (!r.o.project.empty())
+    fprintf(f, "project (load lambda, fold in, foldin.txt): %.3f (%u updates, %u of %u individuals converged)\n", t.project, t.project_iters_run,
+            t.project_converged, r.o.n);
   if (r.o.logl) fprintf(f, "training likelihood (-logl): %.3f (%u evaluations)\n", t.logl, t.logls);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
+}
+
+// -project: the checkpoint's lambda into every context in chunks, tsamd_fold_in over all locations from gamma = 1 (no
+// validation sample is drawn: every stored genotype counts), then theta.txt / gamma.txt through the usual writer and
+// foldin.txt: individual, updates applied, change of the last one
+void project(Run &r, const ckpt::Buf &loc) {
+  Stopwatch sw;
+  const Options &o = r.o;
+  const size_t J = 2 * (size_t)o.k;
+  const double *lam = (const double *)(loc.data() + sizeof(ckpt::BlobHeader));  // (128-byte header: as aligned as the buffer)
+  const uint32_t chunk = std::max<uint32_t>(1u, (uint32_t)std::min<size_t>(o.l, (64u << 20) / (J * sizeof(double))));
+  for (tsamd_ctx *c : r.ctxs) {
+    r.ctx = c;
+    for (uint32_t l0 = 0; l0 < o.l; l0 += chunk) TS(r, tsamd_set_lambda_range(c, l0, std::min(chunk, o.l - l0), lam + (size_t)l0 * J));
+  }
+  r.ctx = r.ctxs[0];
+  printf("+ projecting %u individuals onto the lambda of %s\n", o.n, o.project.c_str());
+  fflush(stdout);
+  std::vector<uint32_t> iters(o.n);
+  std::vector<double> change(o.n);
+  for (size_t i = 0; i < r.ctxs.size(); ++i) {
+    uint32_t b, c, conv = 0, ran = 0;
+    shard_span(r, i, b, c);
+    r.ctx = r.ctxs[i];
+    TS(r, tsamd_fold_in(r.ctxs[i], nullptr, o.l, o.project_iters, o.project_tol, iters.data() + b, change.data() + b, &conv, &ran));
+    r.tm.project_converged += conv;
+    r.tm.project_iters_run = std::max(r.tm.project_iters_run, ran);
+  }
+  r.ctx = r.ctxs[0];
+  r.lerr("projected onto %s: %u updates, %u of %u individuals converged (tol %g)", o.project.c_str(), r.tm.project_iters_run, r.tm.project_converged,
+         o.n, o.project_tol);
+  save_model(r, false);
+  FILE *f = fopen(r.file_str("/foldin.txt").c_str(), "w");
+  if (!f) {
+    fprintf(stderr, "cannot open foldin.txt: %s\n", strerror(errno));
+    exit(-1);
+  }
+  for (uint32_t n = 0; n < o.n; ++n) fprintf(f, "%u\t%u\t%.8e\n", n, iters[n], change[n]);
+  fclose(f);
+  r.tm.project = sw.lap();
+  finish_saves(r);
+  write_timing(r);
+  printf("+ done: %u updates, %u of %u individuals converged\n", r.tm.project_iters_run, r.tm.project_converged, o.n);
 }
 
 // compute_likelihood(first, validation = true) (src/snpsamplinge.cc:461-544);
@@ -1122,6 +1184,12 @@ int main(int argc, char **argv) {
       o.checkpoint = true;
     } else if (!strcmp(a, "-resume")) {
       o.resume = need(a);
+    } else if (!strcmp(a, "-project")) {
+      o.project = need(a);
+    } else if (!strcmp(a, "-project-iters")) {
+      o.project_iters = (uint32_t)atoi(need(a));
+    } else if (!strcmp(a, "-project-tol")) {
+      o.project_tol = atof(need(a));
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -1137,6 +1205,10 @@ int main(int argc, char **argv) {
     return 0;
   }
 
+  if (!o.project.empty() && (!o.resume.empty() || o.compute_beta)) {
+    fprintf(stderr, "error: -project fits a cohort against a trained model; it does not go with %s\n", o.compute_beta ? "-compute-beta" : "-resume");
+    return -1;
+  }
   // -resume: the file is read and checked against the flags before anything else exists -- a checkpoint of another run,
   // a truncated or a corrupt one is refused with nothing written (the engine validates its parts once more on import)
   ckpt::FileHeader resume_head{};
@@ -1155,6 +1227,21 @@ int main(int argc, char **argv) {
       return -1;
     }
     r.tm.resume = resume_sw.lap();
+  }
+
+  // -project: likewise -- the file's lambda is read and checked against -l / -k before anything else exists
+  ckpt::FileHeader project_head{};
+  ckpt::Buf project_loc;
+  if (!o.project.empty()) {
+    if (o.project_iters == 0 || !(o.project_tol >= 0.0) || !std::isfinite(o.project_tol)) {
+      fprintf(stderr, "error: -project-iters must be positive, -project-tol finite and not negative\n");
+      return -1;
+    }
+    std::string why;
+    if (!ckpt::read_loc_part(o.project, o.l, o.k, &project_head, &project_loc, &why)) {
+      fprintf(stderr, "error: -project: %s\n", why.c_str());
+      return -1;
+    }
   }
 
   // the GPU context comes first so that a missing device fails before any output exists
@@ -1206,6 +1293,12 @@ int main(int argc, char **argv) {
   r.plog_u("individuals n", o.n);
   r.plog_u("locations l", o.l);
   r.plog_u("populations k", o.k);
+
+  if (!o.project.empty()) {
+    project(r, project_loc);
+    destroy_all(r);
+    return 0;
+  }
 
   Mt19937 rng(0);  // gsl_rng_alloc: default seed 0 -> 4357
   if (o.seed) rng.set((unsigned long)o.seed);

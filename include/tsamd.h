@@ -67,8 +67,9 @@ typedef struct tsamd_config {
 #define TSAMD_FLAG_TEST_HOOKS 4u     /* honour the TSAMD_TEST_* environment hooks (tests only): those of the peer-to-peer exchange, and
                                         TSAMD_TEST_MAX_WORKGROUPS (the resident kernels' launch geometry as on a device with that
                                         many compute units: small shards then run the many-items-per-thread paths; for
-                                        tsamd_train_loglik, its segment count) and TSAMD_TEST_LOGLIK_CHUNK (locations per
-                                        internal chunk of tsamd_train_loglik) */
+                                        tsamd_train_loglik and tsamd_fold_in, their segment count), TSAMD_TEST_LOGLIK_CHUNK (locations
+                                        per internal chunk of tsamd_train_loglik) and TSAMD_TEST_FOLDIN_SEGMENTS (tsamd_fold_in: cut
+                                        the list into at most that many segments, whatever the device's size) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -139,6 +140,11 @@ int tsamd_set_lambda(tsamd_ctx *ctx, uint32_t loc, const double *lambda);
 int tsamd_get_lambda(tsamd_ctx *ctx, uint32_t first_loc, uint32_t n_locs, double *lambda /* [n_locs][k][2] */);
 int tsamd_get_ebeta(tsamd_ctx *ctx, uint32_t first_loc, uint32_t n_locs, double *ebeta /* [n_locs][k] */);
 int tsamd_get_elogbeta(tsamd_ctx *ctx, uint32_t first_loc, uint32_t n_locs, double *elogbeta /* [n_locs][k][2] */);
+/* tsamd_set_lambda for locations first_loc .. first_loc + n_locs - 1 at once: the same validation (every value positive
+ * and finite, the range inside 0 .. l-1; a refused call leaves the state as it was), ONE copy and ONE Elogbeta refresh
+ * over the range.  How a trained lambda enters a context whose n differs from the run that trained it (tsamd_state_import
+ * refuses a location part written with another n). */
+int tsamd_set_lambda_range(tsamd_ctx *ctx, uint32_t first_loc, uint32_t n_locs, const double *lambda /* [n_locs][k][2] */);
 
 /* replaces one SNPSamplingE::optimize_lambda(loc) call (src/snpsamplinge.cc:320-366)
  * with the -nthreads 1 worker semantics (PhiRunnerE::do_work, :649-686): first the
@@ -199,6 +205,31 @@ int tsamd_heldout_eval(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n, int run
  * rank answers for its own shard and the caller adds the ranks' results: no exchange is involved. */
 int tsamd_train_loglik(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, double *loc_sums, uint32_t *loc_counts,
                        double *indiv_sums, uint32_t *indiv_counts, double *sum, uint64_t *count);
+
+/* Fold-in: fit the gamma of the shard's individuals against the context's lambda, which stays FIXED (csrc/tsamd_foldin_kernels.h).
+ * Starting from the current gamma (tsamd_create: 1, or tsamd_set_gamma), every update replaces an individual's gamma by
+ *   gamma'[n][k] = alpha + w_k * sum over the listed locations j whose stored code at n is not 01 of
+ *                  y eb[j][k][0] / S0_j + (2 - y) eb[j][k][1] / S1_j,
+ *   w_k = exp(psi(gamma[n][k]) - psi(sum_k gamma[n][k])),  S0_j = sum_k w_k eb[j][k][0],  S1_j = sum_k w_k eb[j][k][1],
+ * eb = exp(Elogbeta) as the context stores it: the batch form of update_gamma / update_phimom / update_phidad
+ * (src/snpsamplinge.cc:627-647, :696-719) with rho = 1 and the sum over the locations in place of gamma_scale x one
+ * location.  Missing entries, entries held out by tsamd_set_heldout and padding contribute nothing; a repeated location
+ * counts again.  change = mean_k |gamma' - gamma| / mean_k gamma'.  An individual whose change < tol after an update
+ * keeps that update and is frozen for the rest of the call (its result depends on no other individual); tol == 0 never
+ * converges: exactly max_iters updates run.  The call ends when every individual is frozen or after max_iters updates.
+ * locs == NULL means locations 0 .. n_locs-1 (n_locs <= l).  indiv_iters / indiv_change [shard_count] (may be NULL):
+ * updates applied to each individual and the change of its last one; n_converged (may be NULL): individuals frozen;
+ * iters_run (may be NULL): updates the call ran.
+ * Changes gamma and the stored exp(Elogtheta) of the shard's individuals (the latter through the refresh of
+ * tsamd_set_gamma, so every launch mode accepts the state afterwards) and nothing else: lambda, Elogbeta, c_n, counters,
+ * held-out folds and padding individuals stay as they are.  A pending gamma step is DROPPED, as by tsamd_clear_pending.
+ * No floating-point atomics, a fixed summation order: two identical calls from the same state give identical bits.
+ * Synchronous; settles the context first like every getter.  TSAMD_EINVAL for n_locs == 0, a location >= l, max_iters
+ * == 0, or tol negative or not finite; every k the context accepts is served.  On a sharded context every rank folds in
+ * its own shard: no exchange is involved. */
+int tsamd_fold_in(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, uint32_t max_iters, double tol,
+                  uint32_t *indiv_iters /* [shard_count], may be NULL */, double *indiv_change /* [shard_count], may be NULL */,
+                  uint32_t *n_converged /* may be NULL */, uint32_t *iters_run /* may be NULL */);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

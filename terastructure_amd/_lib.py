@@ -57,6 +57,7 @@ SYMBOLS = {
     "tsamd_set_counts": (_int, [_vp, _pu32]),
     "tsamd_get_counts": (_int, [_vp, _pu32]),
     "tsamd_set_lambda": (_int, [_vp, _u32, _pd]),
+    "tsamd_set_lambda_range": (_int, [_vp, _u32, _u32, _pd]),
     "tsamd_get_lambda": (_int, [_vp, _u32, _u32, _pd]),
     "tsamd_get_ebeta": (_int, [_vp, _u32, _u32, _pd]),
     "tsamd_get_elogbeta": (_int, [_vp, _u32, _u32, _pd]),
@@ -70,6 +71,7 @@ SYMBOLS = {
     "tsamd_heldout_loglik": (_int, [_vp, _u32, _pd, _pu32]),
     "tsamd_heldout_eval": (_int, [_vp, _pu32, _u32, _int, _pd, _pu32, _pd, _pu32]),
     "tsamd_train_loglik": (_int, [_vp, _pu32, _u32, _pd, _pu32, _pd, _pu32, _pd, _pu64]),
+    "tsamd_fold_in": (_int, [_vp, _pu32, _u32, _u32, _dbl, _pu32, _pd, _pu32, _pu32]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

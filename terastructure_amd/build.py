@@ -73,6 +73,8 @@ def _units():
                       [f"-DTSAMD_K={k}", "-mllvm", "-disable-machine-licm"]))
     # tsamd_train_loglik's kernels, every K in one unit (csrc/tsamd_loglik.hip)
     units.append((os.path.join(OBJ_DIR, "loglik.o"), os.path.join(CSRC, "tsamd_loglik.hip"), []))
+    # tsamd_fold_in's kernels, likewise (csrc/tsamd_foldin.hip)
+    units.append((os.path.join(OBJ_DIR, "foldin.o"), os.path.join(CSRC, "tsamd_foldin.hip"), []))
     return units
 
 

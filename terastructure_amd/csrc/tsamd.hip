@@ -25,6 +25,7 @@
 #include "tsamd_wide_kernels.h"
 #include "tsamd_plan.h"
 #include "tsamd_loglik_plan.h"
+#include "tsamd_foldin_plan.h"
 #include "tsamd_unit.h"
 
 using namespace tsamd;
@@ -125,6 +126,13 @@ struct tsamd_ctx {
   size_t ll_chunk_cap = 0;
   void *d_ll_acc = nullptr;    // [npad] sums, [npad] counts
   double *d_ll_thn = nullptr;  // [k][npad]
+  // tsamd_fold_in: the segments' partials (foldin_geometry: at most foldin_scratch_bound bytes), per individual the updates applied,
+  // the last change and the frozen flag, the active count and tile flags, the listed locations; allocated on first use
+  double *d_fi_part = nullptr;
+  size_t fi_part_bytes = 0;
+  void *d_fi_ind = nullptr;      // [npad] change, [npad] iters, [npad] frozen, [1 + npad / 256] active
+  uint32_t *d_fi_locs = nullptr;
+  size_t fi_locs_cap = 0;
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -610,6 +618,9 @@ void tsamd_destroy(tsamd_ctx *c) {
   hipFree(c->d_ll_chunk);
   hipFree(c->d_ll_acc);
   hipFree(c->d_ll_thn);
+  hipFree(c->d_fi_part);
+  hipFree(c->d_fi_ind);
+  hipFree(c->d_fi_locs);
   if (c->h_stage) hipHostFree(c->h_stage);
   hipFree(c->d_state);
   for (auto &j : c->journal) {
@@ -1071,6 +1082,29 @@ int tsamd_set_lambda(tsamd_ctx *c, uint32_t loc, const double *lambda) {
   HIP_TRY(c, hipSetDevice(c->dev));
   HIP_TRY(c, hipMemcpyAsync(c->p.lam + (size_t)loc * J, lambda, J * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(ts_export_loc, dim3(1), dim3(256), 0, c->stream, c->p.lam, c->cfg.k, loc, 1u, 2, c->p.eb);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return TSAMD_OK;
+}
+
+int tsamd_set_lambda_range(tsamd_ctx *c, uint32_t first_loc, uint32_t n_locs, const double *lambda) {
+  CHECK_CTX(c);
+  SETTLE(c);
+  if (!lambda) return fail(c, TSAMD_EINVAL, "null lambda");
+  if (int rc = check_locs(c, first_loc, n_locs)) return rc;
+  if (n_locs == 0) return TSAMD_OK;
+  const size_t J = 2 * (size_t)c->cfg.k, total = (size_t)n_locs * J;
+  for (size_t j = 0; j < total; ++j)
+    if (!(lambda[j] > 0.0) || !std::isfinite(lambda[j]))
+      return fail(c, TSAMD_EINVAL, "lambda must be positive and finite (location %u)", first_loc + (uint32_t)(j / J));
+  HIP_TRY(c, hipSetDevice(c->dev));
+  HIP_TRY(c, hipMemcpyAsync(c->p.lam + (size_t)first_loc * J, lambda, total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  const uint32_t per = 1u << 20;  // locations per launch, as in tsamd_create
+  for (uint32_t l0 = 0; l0 < n_locs; l0 += per) {
+    const uint32_t nl = std::min(per, n_locs - l0);
+    hipLaunchKernelGGL(ts_export_loc, dim3((uint32_t)(((uint64_t)nl * c->cfg.k + 255) / 256)), dim3(256), 0, c->stream, c->p.lam, c->cfg.k,
+                       first_loc + l0, nl, 2, c->p.eb);
+  }
+  HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return TSAMD_OK;
 }
@@ -1707,6 +1741,82 @@ int tsamd_train_loglik(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, doub
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (sum) *sum = total;
   if (count) *count = total_cnt;
+  return TSAMD_OK;
+}
+
+// sweep + step per update (csrc/tsamd_foldin_kernels.h); the active count comes back after every step
+int tsamd_fold_in(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t max_iters, double tol, uint32_t *indiv_iters,
+                  double *indiv_change, uint32_t *n_converged, uint32_t *iters_run) {
+  CHECK_CTX(c);
+  if (n_converged) *n_converged = 0;
+  if (iters_run) *iters_run = 0;
+  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (max_iters == 0) return fail(c, TSAMD_EINVAL, "max_iters must be positive");
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(c, TSAMD_EINVAL, "tol must be finite and not negative");
+  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
+  if (locs)
+    for (uint32_t i = 0; i < n_locs; ++i)
+      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
+  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
+  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
+  const uint32_t K = c->cfg.k, np = c->npad;
+  const FoldinGeom g = foldin_geometry(np, K, n_locs, cus, hooks ? env_u32("TSAMD_TEST_FOLDIN_SEGMENTS", 0) : 0u);
+
+  const size_t part_bytes = (size_t)foldin_scratch_bytes(g, np, K);
+  if (part_bytes > c->fi_part_bytes) {
+    hipFree(c->d_fi_part);
+    c->d_fi_part = nullptr, c->fi_part_bytes = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_fi_part, part_bytes));
+    c->fi_part_bytes = part_bytes;
+  }
+  const size_t max_tiles = np / kFoldinBlock;  // (the smallest tile)
+  if (!c->d_fi_ind) HIP_TRY(c, hipMalloc(&c->d_fi_ind, (size_t)np * 16 + (1 + max_tiles) * sizeof(uint32_t)));
+  if (locs && n_locs > c->fi_locs_cap) {
+    hipFree(c->d_fi_locs);
+    c->d_fi_locs = nullptr, c->fi_locs_cap = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_fi_locs, (size_t)n_locs * sizeof(uint32_t)));
+    c->fi_locs_cap = n_locs;
+  }
+  if (locs) HIP_TRY(c, hipMemcpyAsync(c->d_fi_locs, locs, (size_t)n_locs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+
+  FoldinArgs a{};
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.eb = c->p.eb, a.locs = locs ? c->d_fi_locs : nullptr;
+  a.gam = c->p.gam, a.w = c->p.w, a.part = c->d_fi_part;
+  a.change = (double *)c->d_fi_ind;  // (the doubles first: every array starts on a multiple of 8 bytes)
+  a.iters = (uint32_t *)(a.change + np), a.frozen = a.iters + np, a.active = a.frozen + np;
+  a.npad = np, a.n_local = c->n_local, a.K = K, a.n_locs = n_locs, a.nseg = g.nseg, a.seg_len = g.seg_len, a.ntiles = g.ntiles, a.tile_n = g.tile_n;
+  a.alpha = c->p.alpha, a.tol = tol;
+
+  // the pending gamma step is dropped; w is formed from the gamma the call starts from
+  enqueue_begin(c, 0xffffffffu, true);
+  c->tail_step_pending = false;
+  auto refresh_w = [&] {
+    if (c->plan.wide)
+      hipLaunchKernelGGL(ts_refresh_w_wide, dim3((np + 255) / 256), dim3(256), 0, c->stream, c->p);
+    else
+      kPass[K]->launch(kLaunchRefresh, 0, 0, c->stream, c->p, 0, 0, 0u);
+  };
+  refresh_w();
+  foldin_launch_init(a, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  uint32_t active = c->n_local, ran = 0;
+  while (ran < max_iters && active > 0u) {
+    foldin_launch_update(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&active, a.active, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ++ran;
+  }
+  refresh_w();  // the stored exp(Elogtheta), as tsamd_set_gamma leaves it
+  HIP_TRY(c, hipGetLastError());
+  if (indiv_iters) HIP_TRY(c, hipMemcpyAsync(indiv_iters, a.iters, (size_t)c->n_local * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (indiv_change) HIP_TRY(c, hipMemcpyAsync(indiv_change, a.change, (size_t)c->n_local * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_converged) *n_converged = c->n_local - active;
+  if (iters_run) *iters_run = ran;
   return TSAMD_OK;
 }
 

@@ -165,6 +165,13 @@ class Engine:
             raise ValueError("lambda must be [k][2]")
         self._check(self.h.tsamd_set_lambda(self.ctx, loc, _dp(a)))
 
+    def set_lambda_range(self, lam, first_loc=0):
+        """lambda of locations first_loc .. first_loc + len(lam) - 1 in one call -- tsamd_set_lambda_range; lam is [n_locs][k][2]"""
+        a = np.ascontiguousarray(lam, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (self.k, 2):
+            raise ValueError("lambda must be [n_locs][k][2]")
+        self._check(self.h.tsamd_set_lambda_range(self.ctx, first_loc, a.shape[0], _dp(a)))
+
     def get_lambda(self, first_loc=0, n_locs=None):
         n_locs = self.l - first_loc if n_locs is None else n_locs
         out = np.empty((n_locs, self.k, 2), dtype=np.float64)
@@ -254,6 +261,22 @@ class Engine:
         if per_indiv:
             out.update(indiv_sums=ns, indiv_counts=nc)
         return out
+
+    def fold_in(self, locs=None, max_iters=100, tol=0.0):
+        """fit this shard's gamma against the engine's lambda, held fixed, over locs (None: every location) --
+        tsamd_fold_in: dict(iters [shard_count], change [shard_count], n_converged, iters_run).  Starts from the current
+        gamma; an individual whose change falls below tol is frozen; tol = 0 runs exactly max_iters updates."""
+        if locs is None:
+            a, n_locs = None, self.l
+        else:
+            a = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = a.size
+        it = np.zeros(self.shard_count, dtype=np.uint32)
+        ch = np.zeros(self.shard_count, dtype=np.float64)
+        nc, ran = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.h.tsamd_fold_in(self.ctx, None if a is None else _up(a), n_locs, int(max_iters), float(tol),
+                                         _up(it), _dp(ch), C.byref(nc), C.byref(ran)))
+        return dict(iters=it, change=ch, n_converged=nc.value, iters_run=ran.value)
 
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
