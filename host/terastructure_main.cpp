@@ -149,6 +149,8 @@ struct Options {
   std::string project;          // extension: fit this cohort's theta against the lambda of this checkpoint.bin, held fixed
   uint32_t project_iters = 100; // -project: updates per individual, at most
   double project_tol = 1e-5;    // -project: an individual stops when its update changes gamma by less (relative mean change)
+  std::string kinship;          // extension: relatedness of the individuals listed in this file, with the final model
+  double kinship_min = 0.044194173824159216;  // -kinship-min: pairs below are not listed (2^-4.5: third-degree relatives and closer)
 };
 
 struct Timing {
@@ -159,6 +161,8 @@ struct Timing {
   double project = 0;  // -project: loading the lambda, the fold-in, foldin.txt
   uint32_t project_iters_run = 0, project_converged = 0;
   double logl = 0;  // -logl: evaluating the training likelihood and writing its files
+  double kinship = 0;  // -kinship: tsamd_kinship over all locations and writing its files
+  uint32_t kinship_pairs = 0;
   uint32_t logls = 0;
 };
 
@@ -178,6 +182,8 @@ struct Run {
   double prev_h = -2147483647, max_h = -2147483647;
   uint32_t nh = 0;
   Mt19937 *rng = nullptr;  // the run's generator (its state goes into checkpoint.bin)
+  std::vector<uint32_t> kin_ids;  // -kinship: the listed individuals (global ids), read and checked before anything is written
+  size_t kin_shard = 0;           // ... and the context whose shard holds them all
   std::string bed_path;
   std::vector<std::string> labels;      // -idfile: individual labels, echoed into gammasave.txt
   std::vector<uint8_t> text_payload;   // .012 input: the columns re-packed as PLINK codes, kept for read_column
@@ -343,7 +349,13 @@ void usage() {
           "\t\t\t (individual, updates, last change).  Not together with -resume or -compute-beta\n"
           "\t-project-iters <I>\t -project: at most this many updates per individual (default 100)\n"
           "\t-project-tol <t>\t -project: an individual stops once an update changes its gamma by less than this\n"
-          "\t\t\t (mean |change| / mean gamma; default 1e-5; 0: always -project-iters updates)\n");
+          "\t\t\t (mean |change| / mean gamma; default 1e-5; 0: always -project-iters updates)\n"
+          "\t-kinship <file>\t with the final model (a plain run, -resume or -project): admixture-adjusted relatedness (REAP)\n"
+          "\t\t\t of the individuals listed in <file>, one 0-based index per line (at most 32768, all on one\n"
+          "\t\t\t device's shard), over all locations.  Writes kinship.txt (i, j, kinship, sum of the pair's\n"
+          "\t\t\t sqrt(q (1 - q)) products; pairs i < j at or above -kinship-min) and inbreeding.txt (i, 2 kin_ii - 1)\n"
+          "\t-kinship-min <phi>\t -kinship: lowest kinship coefficient listed (default 0.0442 = 2^-4.5: third-degree\n"
+          "\t\t\t relatives and closer; a negative value lists every pair)\n");
   fflush(stdout);
 }
 
@@ -817,9 +829,13 @@ void write_timing(Run &r) {
     fprintf(f, "project (load lambda, fold in, foldin.txt): %.3f (%u updates, %u of %u individuals converged)\n", t.project, t.project_iters_run,
             t.project_converged, r.o.n);
   if (r.o.logl) fprintf(f, "training likelihood (-logl): %.3f (%u evaluations)\n", t.logl, t.logls);
+  if (!r.o.kinship.empty())
+    fprintf(f, "kinship (-kinship): %.3f (%zu individuals, %u pairs listed)\n", t.kinship, r.kin_ids.size(), t.kinship_pairs);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
+
+void kinship(Run &r);  // (-kinship, below)
 
 // -project: the checkpoint's lambda into every context in chunks, tsamd_fold_in over all locations from gamma = 1 (no
 // validation sample is drawn: every stored genotype counts), then theta.txt / gamma.txt through the usual writer and
@@ -859,9 +875,106 @@ void project(Run &r, const ckpt::Buf &loc) {
   for (uint32_t n = 0; n < o.n; ++n) fprintf(f, "%u\t%u\t%.8e\n", n, iters[n], change[n]);
   fclose(f);
   r.tm.project = sw.lap();
+  if (!o.kinship.empty()) kinship(r);  // (the folded-in theta against the file's lambda)
   finish_saves(r);
   write_timing(r);
   printf("+ done: %u updates, %u of %u individuals converged\n", r.tm.project_iters_run, r.tm.project_converged, o.n);
+}
+
+// -kinship: reads the list -- one 0-based individual index per line -- and checks it against -n, TSAMD_KIN_MAX_M and the
+// shards of -devices (tsamd_kinship answers for pairs inside one shard); false and a reason when it cannot be used
+bool read_kinship_ids(Run &r, std::string *why) {
+  const Options &o = r.o;
+  FILE *f = fopen(o.kinship.c_str(), "r");
+  if (!f) {
+    *why = "cannot open " + o.kinship + ": " + strerror(errno);
+    return false;
+  }
+  char line[256];
+  uint32_t lineno = 0;
+  bool ok = true;
+  while (ok && fgets(line, sizeof line, f) != nullptr) {
+    ++lineno;
+    char *e = nullptr;
+    errno = 0;
+    const unsigned long long v = strtoull(line, &e, 10);
+    const char *q = e;
+    while (*q == ' ' || *q == '\t' || *q == '\r' || *q == '\n') ++q;
+    if (e == line && *q == 0) continue;  // an empty line
+    if (e == line || *q != 0 || errno != 0 || strchr(line, '-') != nullptr || v >= o.n) {
+      *why = o.kinship + " line " + std::to_string(lineno) + ": not an individual index below -n " + std::to_string(o.n);
+      ok = false;
+    } else if (r.kin_ids.size() >= TSAMD_KIN_MAX_M) {
+      *why = o.kinship + " lists more than " + std::to_string(TSAMD_KIN_MAX_M) + " individuals";
+      ok = false;
+    } else
+      r.kin_ids.push_back((uint32_t)v);
+  }
+  fclose(f);
+  if (ok && r.kin_ids.empty()) {
+    *why = o.kinship + " lists no individual";
+    ok = false;
+  }
+  if (!ok) return false;
+  const uint32_t world = (uint32_t)std::max<size_t>(1, o.devices.size());
+  for (uint32_t rank = 0; rank < world; ++rank) {
+    uint32_t b = 0, c = 0;
+    tsamd_shard_range(o.n, rank, world, &b, &c);
+    if (r.kin_ids[0] >= b && r.kin_ids[0] - b < c) {
+      r.kin_shard = rank;
+      for (uint32_t id : r.kin_ids)
+        if (id < b || id - b >= c) {
+          *why = "individuals " + std::to_string(r.kin_ids[0]) + " and " + std::to_string(id) + " lie on different devices' shards: pairs across shards are not supported";
+          return false;
+        }
+    }
+  }
+  return true;
+}
+
+// -kinship: tsamd_kinship of the listed individuals over all l locations under the state of the final save_model;
+// kinship.txt "i \t j \t kin \t den" for the pairs i < j (positions in the list give the order, the file's indices the
+// names) with kin >= -kinship-min, inbreeding.txt "i \t 2 kin_ii - 1"; "%.8f" through fmt_fixed8
+void kinship(Run &r) {
+  Stopwatch sw;
+  const Options &o = r.o;
+  const uint32_t m = (uint32_t)r.kin_ids.size();
+  std::vector<double> kin((size_t)m * m), den((size_t)m * m);
+  r.ctx = r.ctxs[r.kin_shard];
+  TS(r, tsamd_kinship(r.ctx, r.kin_ids.data(), m, nullptr, o.l, kin.data(), nullptr, den.data()));
+  r.ctx = r.ctxs[0];
+  FILE *fk = fopen(r.file_str("/kinship.txt").c_str(), "w"), *fi = fopen(r.file_str("/inbreeding.txt").c_str(), "w");
+  if (!fk || !fi) {
+    r.lerr("cannot open kinship.txt / inbreeding.txt:%s\n", strerror(errno));
+    exit(-1);
+  }
+  std::vector<char> buf((size_t)m * (2 * (tsfmt::kMaxLen + 1) + 32));
+  for (uint32_t a = 0; a < m; ++a) {
+    char *p = buf.data();
+    for (uint32_t b = a + 1; b < m; ++b) {
+      const double v = kin[(size_t)a * m + b];
+      if (!(v >= o.kinship_min)) continue;
+      p = tsfmt::fmt_uint(p, r.kin_ids[a]);
+      *p++ = '\t';
+      p = tsfmt::fmt_uint(p, r.kin_ids[b]);
+      *p++ = '\t';
+      p = tsfmt::fmt_fixed8(p, v);
+      *p++ = '\t';
+      p = tsfmt::fmt_fixed8(p, den[(size_t)a * m + b]);
+      *p++ = '\n';
+      r.tm.kinship_pairs++;
+    }
+    fwrite(buf.data(), 1, (size_t)(p - buf.data()), fk);
+    p = tsfmt::fmt_uint(buf.data(), r.kin_ids[a]);
+    *p++ = '\t';
+    p = tsfmt::fmt_fixed8(p, 2.0 * kin[(size_t)a * m + a] - 1.0);
+    *p++ = '\n';
+    fwrite(buf.data(), 1, (size_t)(p - buf.data()), fi);
+  }
+  fclose(fk);
+  fclose(fi);
+  r.tm.kinship += sw.lap();
+  r.lerr("kinship of %u individuals: %u pairs at or above %g", m, r.tm.kinship_pairs, o.kinship_min);
 }
 
 // compute_likelihood(first, validation = true) (src/snpsamplinge.cc:461-544);
@@ -1190,6 +1303,10 @@ int main(int argc, char **argv) {
       o.project_iters = (uint32_t)atoi(need(a));
     } else if (!strcmp(a, "-project-tol")) {
       o.project_tol = atof(need(a));
+    } else if (!strcmp(a, "-kinship")) {
+      o.kinship = need(a);
+    } else if (!strcmp(a, "-kinship-min")) {
+      o.kinship_min = atof(need(a));
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -1240,6 +1357,19 @@ int main(int argc, char **argv) {
     std::string why;
     if (!ckpt::read_loc_part(o.project, o.l, o.k, &project_head, &project_loc, &why)) {
       fprintf(stderr, "error: -project: %s\n", why.c_str());
+      return -1;
+    }
+  }
+
+  // -kinship: the list is read and checked before anything else exists
+  if (!o.kinship.empty()) {
+    if (o.compute_beta || o.ingest_only) {
+      fprintf(stderr, "error: -kinship evaluates a run's final model; it does not go with %s\n", o.compute_beta ? "-compute-beta" : "-ingest-only");
+      return -1;
+    }
+    std::string why;
+    if (!read_kinship_ids(r, &why)) {
+      fprintf(stderr, "error: -kinship: %s\n", why.c_str());
       return -1;
     }
   }
@@ -1438,6 +1568,7 @@ int main(int argc, char **argv) {
   }
   printf("\n");
   if (o.logl) train_likelihood(r, true);  // the state of the final save_model: the per-location and per-individual files
+  if (!o.kinship.empty()) kinship(r);     // likewise
   finish_saves(r);  // gamma.txt / theta.txt complete and closed before the process ends
   write_timing(r);
   destroy_all(r);

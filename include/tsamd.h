@@ -67,9 +67,11 @@ typedef struct tsamd_config {
 #define TSAMD_FLAG_TEST_HOOKS 4u     /* honour the TSAMD_TEST_* environment hooks (tests only): those of the peer-to-peer exchange, and
                                         TSAMD_TEST_MAX_WORKGROUPS (the resident kernels' launch geometry as on a device with that
                                         many compute units: small shards then run the many-items-per-thread paths; for
-                                        tsamd_train_loglik and tsamd_fold_in, their segment count), TSAMD_TEST_LOGLIK_CHUNK (locations
-                                        per internal chunk of tsamd_train_loglik) and TSAMD_TEST_FOLDIN_SEGMENTS (tsamd_fold_in: cut
-                                        the list into at most that many segments, whatever the device's size) */
+                                        tsamd_train_loglik, tsamd_fold_in and tsamd_kinship, their segment count), TSAMD_TEST_LOGLIK_CHUNK
+                                        (locations per internal chunk of tsamd_train_loglik), TSAMD_TEST_FOLDIN_SEGMENTS (tsamd_fold_in:
+                                        cut the list into at most that many segments, whatever the device's size), TSAMD_TEST_KIN_CHUNK
+                                        (locations per internal chunk of tsamd_kinship) and TSAMD_TEST_KIN_SEGMENTS (tsamd_kinship: cut a
+                                        chunk into at most that many segments, whatever the device's size) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -230,6 +232,28 @@ int tsamd_train_loglik(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, do
 int tsamd_fold_in(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, uint32_t max_iters, double tol,
                   uint32_t *indiv_iters /* [shard_count], may be NULL */, double *indiv_change /* [shard_count], may be NULL */,
                   uint32_t *n_converged /* may be NULL */, uint32_t *iters_run /* may be NULL */);
+
+/* Admixture-adjusted relatedness of m listed individuals over a list of locations: the REAP estimator (Thornton et al. 2012) on
+ * the model the context holds; changes no state (gamma, w, lambda, c_n, counters, the pending step and held-out folds stay as they
+ * are).  With q = sum_k Ebeta[j][k] * Etheta[n][k] (the values tsamd_get_ebeta and tsamd_get_theta return at that moment: a
+ * pending gamma step stays pending) and y the stored genotype,
+ *   r(n,j) = y - 2q,  s(n,j) = sqrt(q (1 - q)),  both 0 where the stored code is 01 (missing, held out by tsamd_set_heldout, padding),
+ *   num[a][b] = sum_j r(a,j) r(b,j),  den[a][b] = sum_j s(a,j) s(b,j),  kin[a][b] = num / (4 den)  (0 where den == 0),
+ * so a locus where either individual is unobserved drops out of both sums.  The diagonal is (1 + F) / 2: inbreeding is
+ * 2 kin[a][a] - 1.  indivs holds GLOBAL ids, in any order; a repeated id is a row of its own; all of them must lie in the
+ * context's shard -- pairs across shards or ranks are out of scope (every rank answers for lists inside its own shard; no
+ * exchange is involved).  indivs == NULL means the first m individuals of the shard.  locs == NULL means locations 0 .. n_locs-1
+ * (n_locs <= l); a repeated location counts again.  kin / num / den [m][m] row-major; each may be NULL, not all three.
+ * r and s are computed once per entry; the two products run on the matrix cores (v_mfma_f64_16x16x4_f64,
+ * csrc/tsamd_kin_kernels.h).  No floating-point atomics, a fixed summation order: two identical calls give identical bits, and
+ * the outputs are exactly symmetric (the lower triangle is a copy of the upper).  A pair's result may depend on m and on how the
+ * library cuts the list into chunks and segments -- by rounding only.  Synchronous; settles the context first like every getter.
+ * TSAMD_EINVAL for m == 0, m > TSAMD_KIN_MAX_M, n_locs == 0, a location >= l, an id outside the shard, or all three outputs
+ * NULL; TSAMD_ENOMEM if the accumulators (two [m][m] matrices of doubles, m rounded up to 64) do not fit; every k the context
+ * accepts is served. */
+#define TSAMD_KIN_MAX_M 32768
+int tsamd_kinship(tsamd_ctx *ctx, const uint32_t *indivs, uint32_t m, const uint32_t *locs, uint32_t n_locs,
+                  double *kin /* [m][m], may be NULL */, double *num /* [m][m], may be NULL */, double *den /* [m][m], may be NULL */);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

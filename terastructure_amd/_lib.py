@@ -14,6 +14,7 @@ FLAG_NO_GRAPH = 2
 FLAG_TEST_HOOKS = 4
 LAUNCH_PER_PASS, LAUNCH_PER_SNP, LAUNCH_PER_SCHEDULE = 0, 1, 2  # tsamd_set_launch_mode
 PASS_HIST_BINS = 128
+KIN_MAX_M = 32768  # TSAMD_KIN_MAX_M
 
 
 class Config(C.Structure):
@@ -72,6 +73,7 @@ SYMBOLS = {
     "tsamd_heldout_eval": (_int, [_vp, _pu32, _u32, _int, _pd, _pu32, _pd, _pu32]),
     "tsamd_train_loglik": (_int, [_vp, _pu32, _u32, _pd, _pu32, _pd, _pu32, _pd, _pu64]),
     "tsamd_fold_in": (_int, [_vp, _pu32, _u32, _u32, _dbl, _pu32, _pd, _pu32, _pu32]),
+    "tsamd_kinship": (_int, [_vp, _pu32, _u32, _pu32, _u32, _pd, _pd, _pd]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

@@ -75,6 +75,8 @@ def _units():
     units.append((os.path.join(OBJ_DIR, "loglik.o"), os.path.join(CSRC, "tsamd_loglik.hip"), []))
     # tsamd_fold_in's kernels, likewise (csrc/tsamd_foldin.hip)
     units.append((os.path.join(OBJ_DIR, "foldin.o"), os.path.join(CSRC, "tsamd_foldin.hip"), []))
+    # tsamd_kinship's kernels, likewise (csrc/tsamd_kin.hip)
+    units.append((os.path.join(OBJ_DIR, "kin.o"), os.path.join(CSRC, "tsamd_kin.hip"), []))
     return units
 
 

@@ -26,6 +26,7 @@
 #include "tsamd_plan.h"
 #include "tsamd_loglik_plan.h"
 #include "tsamd_foldin_plan.h"
+#include "tsamd_kin_plan.h"
 #include "tsamd_unit.h"
 
 using namespace tsamd;
@@ -133,6 +134,12 @@ struct tsamd_ctx {
   void *d_fi_ind = nullptr;      // [npad] change, [npad] iters, [npad] frozen, [1 + npad / 256] active
   uint32_t *d_fi_locs = nullptr;
   size_t fi_locs_cap = 0;
+  // tsamd_kinship: r and s of a chunk, the segments' partial tiles (kin_geometry: at most kKinScratchBound bytes each), the call's
+  // two [mpad][mpad] accumulators, the listed individuals' rows and the chunk's locations; allocated on first use
+  double *d_kin_rs = nullptr, *d_kin_part = nullptr, *d_kin_acc = nullptr;
+  size_t kin_rs_bytes = 0, kin_part_bytes = 0, kin_acc_bytes = 0;
+  uint32_t *d_kin_idx = nullptr;  // [mpad] rows, then [chunk] locations
+  size_t kin_idx_cap = 0;
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -621,6 +628,10 @@ void tsamd_destroy(tsamd_ctx *c) {
   hipFree(c->d_fi_part);
   hipFree(c->d_fi_ind);
   hipFree(c->d_fi_locs);
+  hipFree(c->d_kin_rs);
+  hipFree(c->d_kin_part);
+  hipFree(c->d_kin_acc);
+  hipFree(c->d_kin_idx);
   if (c->h_stage) hipHostFree(c->h_stage);
   hipFree(c->d_state);
   for (auto &j : c->journal) {
@@ -1817,6 +1828,93 @@ int tsamd_fold_in(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (n_converged) *n_converged = c->n_local - active;
   if (iters_run) *iters_run = ran;
+  return TSAMD_OK;
+}
+
+// r and s of a chunk once (ts_kin_resid), then the two symmetric products tile pair by tile pair (ts_kin_syrk, ts_kin_finish:
+// csrc/tsamd_kin_kernels.h), chunk after chunk; reads the state only.
+int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32_t *locs, uint32_t n_locs, double *kin, double *num,
+                  double *den) {
+  CHECK_CTX(c);
+  if (m == 0) return fail(c, TSAMD_EINVAL, "m must be positive");
+  if (m > TSAMD_KIN_MAX_M) return fail(c, TSAMD_EINVAL, "m = %u exceeds TSAMD_KIN_MAX_M = %u", m, (uint32_t)TSAMD_KIN_MAX_M);
+  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (!kin && !num && !den) return fail(c, TSAMD_EINVAL, "kin, num and den are all NULL");
+  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
+  if (locs)
+    for (uint32_t i = 0; i < n_locs; ++i)
+      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (!indivs && m > c->n_local) return fail(c, TSAMD_EINVAL, "m = %u exceeds the shard's %u individuals (indivs == NULL: its first m)", m, c->n_local);
+  if (indivs)
+    for (uint32_t i = 0; i < m; ++i)
+      if (indivs[i] < c->n_begin || indivs[i] - c->n_begin >= c->n_local)
+        return fail(c, TSAMD_EINVAL, "indivs[%u] = %u is outside the shard [%u, %u)", i, indivs[i], c->n_begin, c->n_begin + c->n_local);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
+  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
+  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
+  static_assert(TSAMD_KIN_MAX_M == kKinMaxM, "the header's bound is the plan's");
+  KinGeom g = kin_geometry(m, cus, hooks ? env_u32("TSAMD_TEST_KIN_CHUNK", 0) : 0u, hooks ? env_u32("TSAMD_TEST_KIN_SEGMENTS", 0) : 0u);
+  g.chunk = std::min(g.chunk, n_locs);
+  const uint32_t chunk4 = kin_round_step(g.chunk);
+
+  auto grow = [&](double **p, size_t *have, size_t need) -> hipError_t {
+    if (need <= *have) return hipSuccess;
+    hipFree(*p);
+    *p = nullptr, *have = 0;
+    hipError_t e = hipMalloc((void **)p, need);
+    if (e == hipSuccess) *have = need;
+    return e;
+  };
+  HIP_TRY(c, grow(&c->d_kin_rs, &c->kin_rs_bytes, (size_t)kin_rs_bytes(g)));
+  HIP_TRY(c, grow(&c->d_kin_part, &c->kin_part_bytes, (size_t)kin_part_bytes(g)));
+  HIP_TRY(c, grow(&c->d_kin_acc, &c->kin_acc_bytes, (size_t)kin_acc_bytes(g)));
+  if ((size_t)g.mpad + g.chunk > c->kin_idx_cap) {
+    hipFree(c->d_kin_idx);
+    c->d_kin_idx = nullptr, c->kin_idx_cap = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_kin_idx, ((size_t)g.mpad + g.chunk) * sizeof(uint32_t)));
+    c->kin_idx_cap = (size_t)g.mpad + g.chunk;
+  }
+  uint32_t *d_ids = c->d_kin_idx, *d_locs = d_ids + g.mpad;
+  const size_t mm = (size_t)g.mpad * g.mpad;
+  double *d_num = c->d_kin_acc, *d_den = d_num + mm;
+
+  std::vector<uint32_t> h_ids(g.mpad, 0xffffffffu), h_locs(g.chunk);
+  for (uint32_t i = 0; i < m; ++i) h_ids[i] = indivs ? indivs[i] - c->n_begin : i;
+  HIP_TRY(c, hipMemcpyAsync(d_ids, h_ids.data(), (size_t)g.mpad * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(d_num, 0, 2 * mm * sizeof(double), c->stream));
+
+  KinArgs a{};
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam, a.ids = d_ids, a.locs = d_locs;
+  a.npad = c->npad, a.K = c->cfg.k, a.mpad = g.mpad, a.ntiles = g.ntiles;
+  a.r = c->d_kin_rs, a.s = a.r + (size_t)chunk4 * g.mpad, a.part = c->d_kin_part, a.num = d_num, a.den = d_den;
+  for (uint32_t off = 0; off < n_locs; off += g.chunk) {
+    const uint32_t len = std::min(g.chunk, n_locs - off);
+    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
+    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    a.len = len, a.len4 = kin_round_step(len);
+    const KinSegs sg = kin_segments(g, len);
+    kin_launch_resid(a, c->stream);
+    for (uint32_t p0 = 0; p0 < g.npairs; p0 += g.pairs_per_launch)
+      kin_launch_pairs(a, p0, std::min(g.pairs_per_launch, g.npairs - p0), sg, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (h_locs is reused)
+  }
+  kin_launch_mirror(d_num, d_den, g.mpad, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  auto fetch = [&](double *dst, const double *src) {
+    return hipMemcpy2DAsync(dst, (size_t)m * sizeof(double), src, (size_t)g.mpad * sizeof(double), (size_t)m * sizeof(double), m,
+                            hipMemcpyDeviceToHost, c->stream);
+  };
+  if (num) HIP_TRY(c, fetch(num, d_num));
+  if (den) HIP_TRY(c, fetch(den, d_den));
+  if (kin) {
+    kin_launch_form(d_num, d_den, g.mpad, c->stream);  // (over num, which has been copied out)
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, fetch(kin, d_num));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return TSAMD_OK;
 }
 

@@ -278,6 +278,27 @@ class Engine:
                                          _up(it), _dp(ch), C.byref(nc), C.byref(ran)))
         return dict(iters=it, change=ch, n_converged=nc.value, iters_run=ran.value)
 
+    def kinship(self, indivs=None, locs=None, parts=False):
+        """admixture-adjusted relatedness (REAP) of the listed individuals (GLOBAL ids inside this engine's shard; None: the
+        whole shard) over locs (None: every location) -- tsamd_kinship: kin [m][m], or (kin, num, den) when parts is true.
+        The diagonal is (1 + F) / 2.  Changes no state."""
+        if indivs is None:
+            ia, m = None, self.shard_count
+        else:
+            ia = np.ascontiguousarray(indivs, dtype=np.uint32)
+            m = ia.size
+        if locs is None:
+            la, n_locs = None, self.l
+        else:
+            la = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = la.size
+        kin = np.zeros((m, m), dtype=np.float64)
+        num = np.zeros((m, m), dtype=np.float64) if parts else None
+        den = np.zeros((m, m), dtype=np.float64) if parts else None
+        self._check(self.h.tsamd_kinship(self.ctx, None if ia is None else _up(ia), m, None if la is None else _up(la), n_locs,
+                                         _dp(kin), None if num is None else _dp(num), None if den is None else _dp(den)))
+        return (kin, num, den) if parts else kin
+
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
         """(indiv_bytes, loc_bytes) of the two state blobs -- tsamd_state_sizes"""
