@@ -28,6 +28,8 @@
 #include <fcntl.h>
 
 #include <algorithm>
+#include <limits>
+#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <map>
@@ -151,6 +153,8 @@ struct Options {
   double project_tol = 1e-5;    // -project: an individual stops when its update changes gamma by less (relative mean change)
   std::string kinship;          // extension: relatedness of the individuals listed in this file, with the final model
   double kinship_min = 0.044194173824159216;  // -kinship-min: pairs below are not listed (2^-4.5: third-degree relatives and closer)
+  bool scan = false;            // extension: per-SNP fit and association tests of the final model (scan.txt)
+  std::string pheno;            // -scan: one trait value per individual from this file
 };
 
 struct Timing {
@@ -163,6 +167,7 @@ struct Timing {
   double logl = 0;  // -logl: evaluating the training likelihood and writing its files
   double kinship = 0;  // -kinship: tsamd_kinship over all locations and writing its files
   uint32_t kinship_pairs = 0;
+  double scan = 0;  // -scan: tsamd_snp_scan over all locations and writing scan.txt
   uint32_t logls = 0;
 };
 
@@ -184,6 +189,7 @@ struct Run {
   Mt19937 *rng = nullptr;  // the run's generator (its state goes into checkpoint.bin)
   std::vector<uint32_t> kin_ids;  // -kinship: the listed individuals (global ids), read and checked before anything is written
   size_t kin_shard = 0;           // ... and the context whose shard holds them all
+  std::vector<double> pheno;      // -pheno: the trait (NaN = not phenotyped), read and checked before anything is written
   std::string bed_path;
   std::vector<std::string> labels;      // -idfile: individual labels, echoed into gammasave.txt
   std::vector<uint8_t> text_payload;   // .012 input: the columns re-packed as PLINK codes, kept for read_column
@@ -355,7 +361,13 @@ void usage() {
           "\t\t\t device's shard), over all locations.  Writes kinship.txt (i, j, kinship, sum of the pair's\n"
           "\t\t\t sqrt(q (1 - q)) products; pairs i < j at or above -kinship-min) and inbreeding.txt (i, 2 kin_ii - 1)\n"
           "\t-kinship-min <phi>\t -kinship: lowest kinship coefficient listed (default 0.0442 = 2^-4.5: third-degree\n"
-          "\t\t\t relatives and closer; a negative value lists every pair)\n");
+          "\t\t\t relatives and closer; a negative value lists every pair)\n"
+          "\t-scan\t\t with the final model (a plain run, -resume or -project): per-SNP tests adjusted for structure.\n"
+          "\t\t\t Writes scan.txt: loc, n, O0, O1, O2 (genotype counts), E0, E1, E2 (expected under Binomial(2, q)),\n"
+          "\t\t\t z_het, p_het (heterozygote count against the model), z_freq, p_freq (allele count against it)\n"
+          "\t-pheno <file>\t -scan: one trait value per line (theta.txt's order, exactly -n lines; NA or nan = not\n"
+          "\t\t\t phenotyped); scan.txt gains n_t, z_trait, p_trait: the score test of the trait against the\n"
+          "\t\t\t genotype residual y - 2q\n");
   fflush(stdout);
 }
 
@@ -831,11 +843,13 @@ void write_timing(Run &r) {
   if (r.o.logl) fprintf(f, "training likelihood (-logl): %.3f (%u evaluations)\n", t.logl, t.logls);
   if (!r.o.kinship.empty())
     fprintf(f, "kinship (-kinship): %.3f (%zu individuals, %u pairs listed)\n", t.kinship, r.kin_ids.size(), t.kinship_pairs);
+  if (r.o.scan) fprintf(f, "scan (-scan): %.3f (%u locations%s)\n", t.scan, r.o.l, r.o.pheno.empty() ? "" : ", with a trait");
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
 
 void kinship(Run &r);  // (-kinship, below)
+void scan(Run &r);     // (-scan, below)
 
 // -project: the checkpoint's lambda into every context in chunks, tsamd_fold_in over all locations from gamma = 1 (no
 // validation sample is drawn: every stored genotype counts), then theta.txt / gamma.txt through the usual writer and
@@ -876,6 +890,7 @@ void project(Run &r, const ckpt::Buf &loc) {
   fclose(f);
   r.tm.project = sw.lap();
   if (!o.kinship.empty()) kinship(r);  // (the folded-in theta against the file's lambda)
+  if (o.scan) scan(r);                 // likewise
   finish_saves(r);
   write_timing(r);
   printf("+ done: %u updates, %u of %u individuals converged\n", r.tm.project_iters_run, r.tm.project_converged, o.n);
@@ -975,6 +990,93 @@ void kinship(Run &r) {
   fclose(fi);
   r.tm.kinship += sw.lap();
   r.lerr("kinship of %u individuals: %u pairs at or above %g", m, r.tm.kinship_pairs, o.kinship_min);
+}
+
+// -pheno: reads the trait -- one value per line in theta.txt's order, NA or nan for an individual that is not phenotyped --
+// and checks it against -n; false and a reason when it cannot be used
+bool read_pheno(Run &r, std::string *why) {
+  const Options &o = r.o;
+  FILE *f = fopen(o.pheno.c_str(), "r");
+  if (!f) {
+    *why = "cannot open " + o.pheno + ": " + strerror(errno);
+    return false;
+  }
+  char line[256];
+  uint32_t lineno = 0;
+  bool ok = true;
+  while (ok && fgets(line, sizeof line, f) != nullptr) {
+    ++lineno;
+    char *b = line;
+    while (*b == ' ' || *b == '\t') ++b;
+    char *e = b + strlen(b);
+    while (e > b && (e[-1] == ' ' || e[-1] == '\t' || e[-1] == '\r' || e[-1] == '\n')) --e;
+    *e = 0;
+    double v = std::numeric_limits<double>::quiet_NaN();
+    if (strcmp(b, "NA") != 0 && strcmp(b, "nan") != 0) {
+      char *end = nullptr;
+      v = strtod(b, &end);
+      if (end == b || *end != 0 || !std::isfinite(v)) {
+        *why = o.pheno + " line " + std::to_string(lineno) + ": not a finite number, NA or nan";
+        ok = false;
+      }
+    }
+    if (ok && r.pheno.size() >= o.n) {
+      *why = o.pheno + " line " + std::to_string(lineno) + ": more lines than -n " + std::to_string(o.n);
+      ok = false;
+    }
+    if (ok) r.pheno.push_back(v);
+  }
+  fclose(f);
+  if (ok && r.pheno.size() != o.n) {
+    *why = o.pheno + " has " + std::to_string(r.pheno.size()) + " lines, -n is " + std::to_string(o.n);
+    ok = false;
+  }
+  return ok;
+}
+
+// -scan: tsamd_snp_scan over all l locations under the state of the final save_model, the trait sliced by shard and the
+// shards' rows added in shard order; every z and p from tsamd_scan_statistics.  scan.txt, one line per location:
+// "loc \t n \t O0 \t O1 \t O2 \t E0 \t E1 \t E2 \t z_het \t p_het \t z_freq \t p_freq" and with -pheno "\t n_t \t z_trait \t p_trait"
+void scan(Run &r) {
+  Stopwatch sw;
+  const Options &o = r.o;
+  const uint32_t l = o.l;
+  const bool trait = !o.pheno.empty();
+  std::vector<double> fs((size_t)l * TSAMD_SCAN_FIT_SUMS, 0.0), ts(trait ? (size_t)l * TSAMD_SCAN_TRAIT_SUMS : 0, 0.0), s1(fs.size()), t1(ts.size());
+  std::vector<uint32_t> fc((size_t)l * TSAMD_SCAN_FIT_COUNTS, 0u), tc(trait ? l : 0, 0u), c1(fc.size()), n1(tc.size());
+  for (size_t i = 0; i < r.ctxs.size(); ++i) {  // shard after shard; no exchange is involved
+    uint32_t b, c;
+    shard_span(r, i, b, c);
+    r.ctx = r.ctxs[i];
+    TS(r, tsamd_snp_scan(r.ctxs[i], nullptr, l, trait ? r.pheno.data() + b : nullptr, s1.data(), c1.data(), trait ? t1.data() : nullptr,
+                         trait ? n1.data() : nullptr));
+    for (size_t x = 0; x < fs.size(); ++x) fs[x] += s1[x];
+    for (size_t x = 0; x < fc.size(); ++x) fc[x] += c1[x];
+    for (size_t x = 0; x < ts.size(); ++x) ts[x] += t1[x];
+    for (size_t x = 0; x < tc.size(); ++x) tc[x] += n1[x];
+  }
+  r.ctx = r.ctxs[0];
+  std::vector<double> st((size_t)l * TSAMD_SCAN_STATS);
+  if (tsamd_scan_statistics(fs.data(), fc.data(), trait ? ts.data() : nullptr, trait ? tc.data() : nullptr, l, st.data()) != 0) {
+    r.lerr("tsamd_scan_statistics: %s\n", tsamd_last_error(nullptr));
+    exit(-1);
+  }
+  FILE *f = fopen(r.file_str("/scan.txt").c_str(), "w");
+  if (!f) {
+    r.lerr("cannot open scan.txt:%s\n", strerror(errno));
+    exit(-1);
+  }
+  for (uint32_t j = 0; j < l; ++j) {
+    const double *s = &fs[(size_t)j * TSAMD_SCAN_FIT_SUMS], *z = &st[(size_t)j * TSAMD_SCAN_STATS];
+    const uint32_t *c = &fc[(size_t)j * TSAMD_SCAN_FIT_COUNTS];
+    fprintf(f, "%u\t%u\t%u\t%u\t%u\t%.8f\t%.8f\t%.8f\t%.6f\t%.6e\t%.6f\t%.6e", j, c[0] + c[1] + c[2], c[0], c[1], c[2], s[0], s[1], s[2], z[0], z[1],
+            z[2], z[3]);
+    if (trait) fprintf(f, "\t%u\t%.6f\t%.6e", tc[j], z[4], z[5]);
+    fputc('\n', f);
+  }
+  fclose(f);
+  r.tm.scan += sw.lap();
+  r.lerr("scan of %u locations%s", l, trait ? " with a trait" : "");
 }
 
 // compute_likelihood(first, validation = true) (src/snpsamplinge.cc:461-544);
@@ -1307,6 +1409,10 @@ int main(int argc, char **argv) {
       o.kinship = need(a);
     } else if (!strcmp(a, "-kinship-min")) {
       o.kinship_min = atof(need(a));
+    } else if (!strcmp(a, "-scan")) {
+      o.scan = true;
+    } else if (!strcmp(a, "-pheno")) {
+      o.pheno = need(a);
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -1370,6 +1476,23 @@ int main(int argc, char **argv) {
     std::string why;
     if (!read_kinship_ids(r, &why)) {
       fprintf(stderr, "error: -kinship: %s\n", why.c_str());
+      return -1;
+    }
+  }
+
+  // -scan / -pheno: the trait is read and checked before anything else exists
+  if (!o.pheno.empty() && !o.scan) {
+    fprintf(stderr, "error: -pheno gives -scan its trait; it needs -scan\n");
+    return -1;
+  }
+  if (o.scan) {
+    if (o.compute_beta || o.ingest_only) {
+      fprintf(stderr, "error: -scan evaluates a run's final model; it does not go with %s\n", o.compute_beta ? "-compute-beta" : "-ingest-only");
+      return -1;
+    }
+    std::string why;
+    if (!o.pheno.empty() && !read_pheno(r, &why)) {
+      fprintf(stderr, "error: -pheno: %s\n", why.c_str());
       return -1;
     }
   }
@@ -1569,6 +1692,7 @@ int main(int argc, char **argv) {
   printf("\n");
   if (o.logl) train_likelihood(r, true);  // the state of the final save_model: the per-location and per-individual files
   if (!o.kinship.empty()) kinship(r);     // likewise
+  if (o.scan) scan(r);                    // likewise
   finish_saves(r);  // gamma.txt / theta.txt complete and closed before the process ends
   write_timing(r);
   destroy_all(r);

@@ -70,8 +70,10 @@ typedef struct tsamd_config {
                                         tsamd_train_loglik, tsamd_fold_in and tsamd_kinship, their segment count), TSAMD_TEST_LOGLIK_CHUNK
                                         (locations per internal chunk of tsamd_train_loglik), TSAMD_TEST_FOLDIN_SEGMENTS (tsamd_fold_in:
                                         cut the list into at most that many segments, whatever the device's size), TSAMD_TEST_KIN_CHUNK
-                                        (locations per internal chunk of tsamd_kinship) and TSAMD_TEST_KIN_SEGMENTS (tsamd_kinship: cut a
-                                        chunk into at most that many segments, whatever the device's size) */
+                                        (locations per internal chunk of tsamd_kinship), TSAMD_TEST_KIN_SEGMENTS (tsamd_kinship: cut a
+                                        chunk into at most that many segments, whatever the device's size) and TSAMD_TEST_SCAN_CHUNK
+                                        (locations per internal chunk of tsamd_snp_scan, whose segment count TSAMD_TEST_MAX_WORKGROUPS
+                                        sets as for the other sweeps) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -254,6 +256,41 @@ int tsamd_fold_in(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, uint32_
 #define TSAMD_KIN_MAX_M 32768
 int tsamd_kinship(tsamd_ctx *ctx, const uint32_t *indivs, uint32_t m, const uint32_t *locs, uint32_t n_locs,
                   double *kin /* [m][m], may be NULL */, double *num /* [m][m], may be NULL */, double *den /* [m][m], may be NULL */);
+
+/* Per-SNP sufficient statistics of the structure-adjusted fit and association tests; changes no state (gamma, w, lambda, c_n,
+ * counters, the pending step and held-out folds stay as they are).  With q = sum_k Ebeta[j][k] * Etheta[n][k] (the values
+ * tsamd_get_ebeta and tsamd_get_theta return at that moment: a pending gamma step stays pending), h = 2q(1-q), y the stored
+ * genotype and r = y - 2q, every listed location gets, over the shard's individuals whose stored code at loc is not 01 (missing,
+ * held out by tsamd_set_heldout, padding), the rows described beside the constants below, in ONE sweep of the listed columns
+ * (csrc/tsamd_scan_kernels.h).  trait [shard_count] holds one value per individual of the shard, NaN for an individual that is
+ * not phenotyped; the trait rows run over the entries that are stored AND phenotyped.  locs == NULL means locations
+ * 0 .. n_locs-1 (n_locs <= l); a repeated location is evaluated again.  No floating-point atomics, a fixed summation order: two
+ * identical calls give identical bits, and a location's rows depend neither on the other locations of the call nor on how the
+ * library cuts the list into chunks and segments.  The counts are exact.  Synchronous; settles the context first like every
+ * getter.  TSAMD_EINVAL for n_locs == 0, a location >= l, all four outputs NULL, a trait output requested with trait == NULL,
+ * trait given with both trait outputs NULL, or a trait value of +-infinity; every k the context accepts is served.  On a
+ * sharded context every rank answers for its own shard; every output is a plain sum, so the caller adds the ranks' rows: no
+ * exchange is involved. */
+#define TSAMD_SCAN_FIT_SUMS 4    /* fit_sums[j][]: E0 = sum (1-q)^2, E1 = sum h, E2 = sum q^2, VH = sum h(1-h) */
+#define TSAMD_SCAN_FIT_COUNTS 3  /* fit_counts[j][]: entries with y = 0, 1, 2 */
+#define TSAMD_SCAN_TRAIT_SUMS 6  /* trait_sums[j][]: sum t, sum t r, sum t^2 h, sum t h, sum r, sum h */
+int tsamd_snp_scan(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs,
+                   const double *trait /* [shard_count], NaN = not phenotyped; may be NULL */,
+                   double *fit_sums /* [n_locs][4], may be NULL */, uint32_t *fit_counts /* [n_locs][3], may be NULL */,
+                   double *trait_sums /* [n_locs][6], may be NULL */, uint32_t *trait_counts /* [n_locs], may be NULL */);
+/* z and p of every location from the rows of tsamd_snp_scan, added across ranks by the caller.  Takes no context and does no
+ * device work: it runs without a GPU.  With O_y = fit_counts[j][y]:
+ *   z_het   = (O1 - E1) / sqrt(VH)                      (exact under the model: O1 is a sum of independent Bernoulli(h));
+ *   z_freq  = ((O1 + 2 O2) - (E1 + 2 E2)) / sqrt(E1)    (allele-count calibration: Var y = h);
+ *   z_trait = U / sqrt(V),  c = sum t / count,  U = sum t r - c sum r,  V = sum t^2 h - 2 c sum t h + c^2 sum h
+ *             (the score test of the trait against the genotype residual, the trait centred among the contributing individuals);
+ *   p = erfc(|z| / sqrt(2)).
+ * Where a denominator is not positive, where count < 2, or where trait_sums or trait_counts is NULL, z = 0 and p = 1.
+ * TSAMD_EINVAL for n_locs == 0 or a NULL fit_sums, fit_counts or stats (the message: tsamd_last_error(NULL)). */
+#define TSAMD_SCAN_STATS 6       /* stats[j][]: z_het, p_het, z_freq, p_freq, z_trait, p_trait */
+int tsamd_scan_statistics(const double *fit_sums, const uint32_t *fit_counts,
+                          const double *trait_sums /* may be NULL */, const uint32_t *trait_counts /* may be NULL */,
+                          uint32_t n_locs, double *stats /* [n_locs][6] */);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

@@ -15,6 +15,7 @@ FLAG_TEST_HOOKS = 4
 LAUNCH_PER_PASS, LAUNCH_PER_SNP, LAUNCH_PER_SCHEDULE = 0, 1, 2  # tsamd_set_launch_mode
 PASS_HIST_BINS = 128
 KIN_MAX_M = 32768  # TSAMD_KIN_MAX_M
+SCAN_FIT_SUMS, SCAN_FIT_COUNTS, SCAN_TRAIT_SUMS, SCAN_STATS = 4, 3, 6, 6  # TSAMD_SCAN_*
 
 
 class Config(C.Structure):
@@ -74,6 +75,8 @@ SYMBOLS = {
     "tsamd_train_loglik": (_int, [_vp, _pu32, _u32, _pd, _pu32, _pd, _pu32, _pd, _pu64]),
     "tsamd_fold_in": (_int, [_vp, _pu32, _u32, _u32, _dbl, _pu32, _pd, _pu32, _pu32]),
     "tsamd_kinship": (_int, [_vp, _pu32, _u32, _pu32, _u32, _pd, _pd, _pd]),
+    "tsamd_snp_scan": (_int, [_vp, _pu32, _u32, _pd, _pd, _pu32, _pd, _pu32]),
+    "tsamd_scan_statistics": (_int, [_pd, _pu32, _pd, _pu32, _u32, _pd]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

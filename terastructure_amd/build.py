@@ -77,6 +77,8 @@ def _units():
     units.append((os.path.join(OBJ_DIR, "foldin.o"), os.path.join(CSRC, "tsamd_foldin.hip"), []))
     # tsamd_kinship's kernels, likewise (csrc/tsamd_kin.hip)
     units.append((os.path.join(OBJ_DIR, "kin.o"), os.path.join(CSRC, "tsamd_kin.hip"), []))
+    # tsamd_snp_scan's kernels, likewise (csrc/tsamd_scan.hip)
+    units.append((os.path.join(OBJ_DIR, "scan.o"), os.path.join(CSRC, "tsamd_scan.hip"), []))
     return units
 
 

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <unordered_set>
@@ -27,6 +28,7 @@
 #include "tsamd_loglik_plan.h"
 #include "tsamd_foldin_plan.h"
 #include "tsamd_kin_plan.h"
+#include "tsamd_scan_plan.h"
 #include "tsamd_unit.h"
 
 using namespace tsamd;
@@ -140,6 +142,13 @@ struct tsamd_ctx {
   size_t kin_rs_bytes = 0, kin_part_bytes = 0, kin_acc_bytes = 0;
   uint32_t *d_kin_idx = nullptr;  // [mpad] rows, then [chunk] locations
   size_t kin_idx_cap = 0;
+  // tsamd_snp_scan: the tiles' partials (scan_geometry: at most kScanScratchBound bytes), the chunk's locations and rows, the trait
+  // padded to npad; allocated on first use
+  double *d_scan_part = nullptr;
+  size_t scan_part_bytes = 0;
+  void *d_scan_chunk = nullptr;  // [chunk][10] sums, [chunk][4] counts, [chunk] locations
+  size_t scan_chunk_cap = 0;
+  double *d_scan_trait = nullptr;  // [npad]
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -632,6 +641,9 @@ void tsamd_destroy(tsamd_ctx *c) {
   hipFree(c->d_kin_part);
   hipFree(c->d_kin_acc);
   hipFree(c->d_kin_idx);
+  hipFree(c->d_scan_part);
+  hipFree(c->d_scan_chunk);
+  hipFree(c->d_scan_trait);
   if (c->h_stage) hipHostFree(c->h_stage);
   hipFree(c->d_state);
   for (auto &j : c->journal) {
@@ -1915,6 +1927,101 @@ int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32
     HIP_TRY(c, fetch(kin, d_num));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return TSAMD_OK;
+}
+
+// One sweep of the listed columns (csrc/tsamd_scan_kernels.h), chunk after chunk; reads the state only.
+int tsamd_snp_scan(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, const double *trait, double *fit_sums, uint32_t *fit_counts,
+                   double *trait_sums, uint32_t *trait_counts) {
+  CHECK_CTX(c);
+  static_assert(TSAMD_SCAN_FIT_SUMS == kScanFitSums && TSAMD_SCAN_FIT_COUNTS == kScanFitCounts && TSAMD_SCAN_TRAIT_SUMS == kScanTraitSums &&
+                    TSAMD_SCAN_STATS == kScanStats,
+                "the header's row lengths are the plan's");
+  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (!fit_sums && !fit_counts && !trait_sums && !trait_counts)
+    return fail(c, TSAMD_EINVAL, "fit_sums, fit_counts, trait_sums and trait_counts are all NULL");
+  if (!trait && (trait_sums || trait_counts)) return fail(c, TSAMD_EINVAL, "trait_sums / trait_counts requested without a trait");
+  if (trait && !trait_sums && !trait_counts) return fail(c, TSAMD_EINVAL, "a trait is given but trait_sums and trait_counts are both NULL");
+  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
+  if (locs)
+    for (uint32_t i = 0; i < n_locs; ++i)
+      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (trait)
+    for (uint32_t i = 0; i < c->n_local; ++i)
+      if (std::isinf(trait[i])) return fail(c, TSAMD_EINVAL, "trait[%u] is infinite (NaN marks an individual without a trait value)", i);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
+  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
+  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
+  const uint32_t K = c->cfg.k, np = c->npad;
+  ScanGeom g = scan_geometry(np, K, trait != nullptr, cus, hooks ? env_u32("TSAMD_TEST_SCAN_CHUNK", 0) : 0u);
+  g.chunk = std::min(g.chunk, n_locs);
+
+  const size_t part_bytes = (size_t)scan_scratch_bytes(g);
+  if (part_bytes > c->scan_part_bytes) {
+    hipFree(c->d_scan_part);
+    c->d_scan_part = nullptr, c->scan_part_bytes = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_scan_part, part_bytes));
+    c->scan_part_bytes = part_bytes;
+  }
+  constexpr size_t kRowSums = kScanFitSums + kScanTraitSums, kRowCounts = kScanFitCounts + 1;
+  if (g.chunk > c->scan_chunk_cap) {
+    hipFree(c->d_scan_chunk);
+    c->d_scan_chunk = nullptr, c->scan_chunk_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->d_scan_chunk, (size_t)g.chunk * (kRowSums * sizeof(double) + (kRowCounts + 1) * sizeof(uint32_t))));
+    c->scan_chunk_cap = g.chunk;
+  }
+  if (trait && !c->d_scan_trait) HIP_TRY(c, hipMalloc((void **)&c->d_scan_trait, (size_t)np * sizeof(double)));
+  if (K > (uint32_t)TSAMD_SPECIALIZED_K && !c->d_ll_thn) HIP_TRY(c, hipMalloc((void **)&c->d_ll_thn, (size_t)K * np * sizeof(double)));
+  // (the doubles first: every array starts on a multiple of 8 bytes)
+  double *d_sums = (double *)c->d_scan_chunk;
+  uint32_t *d_counts = (uint32_t *)(d_sums + c->scan_chunk_cap * kRowSums), *d_locs = d_counts + c->scan_chunk_cap * kRowCounts;
+
+  std::vector<double> h_trait;
+  if (trait) {  // padding individuals carry no trait value
+    h_trait.assign(np, std::numeric_limits<double>::quiet_NaN());
+    std::copy(trait, trait + c->n_local, h_trait.begin());
+    HIP_TRY(c, hipMemcpyAsync(c->d_scan_trait, h_trait.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  if (K > (uint32_t)TSAMD_SPECIALIZED_K) loglik_launch_theta(c->p.gam, np, K, c->d_ll_thn, c->stream);
+  std::vector<uint32_t> h_locs(g.chunk), h_counts((size_t)g.chunk * kRowCounts);
+  std::vector<double> h_sums((size_t)g.chunk * kRowSums);
+  for (uint32_t off = 0; off < n_locs; off += g.chunk) {
+    const uint32_t len = std::min(g.chunk, n_locs - off);
+    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
+    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const ScanSegs sg = scan_segments(g, len);
+    ScanArgs a{};
+    a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.thn = c->d_ll_thn, a.lam = c->p.lam;
+    a.trait = trait ? c->d_scan_trait : nullptr, a.locs = d_locs;
+    a.npad = np, a.K = K, a.len = len, a.seg_len = sg.seg_len, a.ntiles = g.ntiles, a.part = c->d_scan_part;
+    scan_launch_chunk(a, sg.nseg, d_sums, d_counts, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(h_sums.data(), d_sums, (size_t)len * kRowSums * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_counts.data(), d_counts, (size_t)len * kRowCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < len; ++i) {  // listed order
+      const double *s = &h_sums[(size_t)i * kRowSums];
+      const uint32_t *n = &h_counts[(size_t)i * kRowCounts];
+      if (fit_sums) std::copy(s, s + kScanFitSums, fit_sums + (size_t)(off + i) * kScanFitSums);
+      if (fit_counts) std::copy(n, n + kScanFitCounts, fit_counts + (size_t)(off + i) * kScanFitCounts);
+      if (trait_sums) std::copy(s + kScanFitSums, s + kRowSums, trait_sums + (size_t)(off + i) * kScanTraitSums);
+      if (trait_counts) trait_counts[off + i] = n[kScanFitCounts];
+    }
+  }
+  return TSAMD_OK;
+}
+
+// no context, no device work: z and p from the sums the caller has added across ranks (scan_statistics_row, csrc/tsamd_scan_plan.h)
+int tsamd_scan_statistics(const double *fit_sums, const uint32_t *fit_counts, const double *trait_sums, const uint32_t *trait_counts,
+                          uint32_t n_locs, double *stats) {
+  if (n_locs == 0) return fail(nullptr, TSAMD_EINVAL, "n_locs must be positive");
+  if (!fit_sums || !fit_counts || !stats) return fail(nullptr, TSAMD_EINVAL, "fit_sums, fit_counts and stats must not be NULL");
+  const bool trait = trait_sums && trait_counts;
+  for (uint32_t i = 0; i < n_locs; ++i)
+    scan_statistics_row(fit_sums + (size_t)i * kScanFitSums, fit_counts + (size_t)i * kScanFitCounts,
+                        trait ? trait_sums + (size_t)i * kScanTraitSums : nullptr, trait ? trait_counts[i] : 0u, stats + (size_t)i * kScanStats);
   return TSAMD_OK;
 }
 

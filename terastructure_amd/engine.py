@@ -41,6 +41,28 @@ def host_free(arr):
     _lib.load().tsamd_host_free(C.c_void_p(arr.ctypes.data))
 
 
+def scan_statistics(fit_sums, fit_counts, trait_sums=None, trait_counts=None):
+    """[n_locs][6] = z_het, p_het, z_freq, p_freq, z_trait, p_trait from the sufficient statistics of Engine.snp_scan (added
+    across shards by the caller) -- tsamd_scan_statistics.  No device work: runs without a GPU."""
+    h = _lib.load()
+    fs = np.ascontiguousarray(fit_sums, dtype=np.float64).reshape(-1, _lib.SCAN_FIT_SUMS)
+    fc = np.ascontiguousarray(fit_counts, dtype=np.uint32).reshape(-1, _lib.SCAN_FIT_COUNTS)
+    n_locs = fs.shape[0]
+    if fc.shape[0] != n_locs:
+        raise ValueError("fit_sums and fit_counts differ in length")
+    ts = tc = None
+    if trait_sums is not None and trait_counts is not None:
+        ts = np.ascontiguousarray(trait_sums, dtype=np.float64).reshape(-1, _lib.SCAN_TRAIT_SUMS)
+        tc = np.ascontiguousarray(trait_counts, dtype=np.uint32).reshape(-1)
+        if ts.shape[0] != n_locs or tc.shape[0] != n_locs:
+            raise ValueError("trait_sums / trait_counts differ in length from fit_sums")
+    out = np.zeros((n_locs, _lib.SCAN_STATS), dtype=np.float64)
+    rc = h.tsamd_scan_statistics(_dp(fs), _up(fc), None if ts is None else _dp(ts), None if tc is None else _up(tc), n_locs, _dp(out))
+    if rc != 0:
+        raise _lib.TsamdError(rc, h.tsamd_last_error(None).decode())
+    return out
+
+
 class Engine:
     def __init__(self, n, l, k, device=0, rank=0, world=1, flags=0, **overrides):
         self.h = _lib.load()
@@ -298,6 +320,32 @@ class Engine:
         self._check(self.h.tsamd_kinship(self.ctx, None if ia is None else _up(ia), m, None if la is None else _up(la), n_locs,
                                          _dp(kin), None if num is None else _dp(num), None if den is None else _dp(den)))
         return (kin, num, den) if parts else kin
+
+    def snp_scan(self, locs=None, trait=None):
+        """per-location sufficient statistics of the structure-adjusted fit and association tests over locs (None: every
+        location) -- tsamd_snp_scan: dict(fit_sums [n_locs][4], fit_counts [n_locs][3][, trait_sums [n_locs][6], trait_counts
+        [n_locs]]); trait is [shard_count] with NaN for an individual that is not phenotyped.  Every value is a plain sum over
+        this engine's shard: add the shards' arrays, then scan_statistics gives z and p.  Changes no state."""
+        if locs is None:
+            a, n_locs = None, self.l
+        else:
+            a = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = a.size
+        t = None
+        if trait is not None:
+            t = np.ascontiguousarray(trait, dtype=np.float64)
+            if t.shape != (self.shard_count,):
+                raise ValueError(f"trait must be [{self.shard_count}]")
+        fs = np.zeros((n_locs, _lib.SCAN_FIT_SUMS), dtype=np.float64)
+        fc = np.zeros((n_locs, _lib.SCAN_FIT_COUNTS), dtype=np.uint32)
+        ts = np.zeros((n_locs, _lib.SCAN_TRAIT_SUMS), dtype=np.float64) if t is not None else None
+        tc = np.zeros(n_locs, dtype=np.uint32) if t is not None else None
+        self._check(self.h.tsamd_snp_scan(self.ctx, None if a is None else _up(a), n_locs, None if t is None else _dp(t), _dp(fs), _up(fc),
+                                          None if ts is None else _dp(ts), None if tc is None else _up(tc)))
+        out = dict(fit_sums=fs, fit_counts=fc)
+        if t is not None:
+            out.update(trait_sums=ts, trait_counts=tc)
+        return out
 
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
