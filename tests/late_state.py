@@ -14,7 +14,8 @@ class Late:
     """n, l, k, l_eff, y [l][n] (3 = missing), payload, gamma [n][k], counts [n], lam [l][k][2], held {loc: indivs}"""
 
 
-def plant(n, l, k, seed, l_eff=5e5, held_locs=(1, 4, 6), missing_rate=0.02):
+def plant(n, l, k, seed, l_eff=5e5, held_locs=(1, 4, 6), missing_rate=0.02, n_eff=None):
+    """n_eff: the sample size lambda is scaled to (None: n itself); 1e6 puts Ebeta within 1e-6 of 0 and 1 at a small n"""
     rng = np.random.default_rng(seed)
     alpha, eta = 1.0 / k, 1.0
     theta = rng.dirichlet(np.full(k, 0.05), size=n)                  # [n][k]
@@ -34,11 +35,12 @@ def plant(n, l, k, seed, l_eff=5e5, held_locs=(1, 4, 6), missing_rate=0.02):
     counts = rng.integers(0, 20_001, size=n).astype(np.uint32)
     counts[rng.choice(n, size=8, replace=False)] = 0
     counts[rng.choice(n, size=8, replace=False)] = (1_000_000 - rng.integers(0, 1000, size=8)).astype(np.uint32)
-    # lambda = eta + 2 N share_k (beta, 1 - beta)
+    # lambda = eta + 2 N share_k (beta, 1 - beta), N = n_eff where given
     share = theta.mean(axis=0)
+    pop = n if n_eff is None else n_eff
     lam = np.empty((l, k, 2))
-    lam[:, :, 0] = eta + 2.0 * n * share[None, :] * beta
-    lam[:, :, 1] = eta + 2.0 * n * share[None, :] * (1.0 - beta)
+    lam[:, :, 0] = eta + 2.0 * pop * share[None, :] * beta
+    lam[:, :, 1] = eta + 2.0 * pop * share[None, :] * (1.0 - beta)
     held = {}
     for loc in held_locs:
         cand = np.nonzero(y[loc] != 3)[0]
