@@ -186,14 +186,18 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // serves both r and 1/z.
 // Lets the gamma step form w[k] = z_k * exp(a_k - a_max) -- exp(Elogtheta) up to a
 // per-individual factor -- with one exp and no log per population.
-__device__ __forceinline__ void exp_digamma_split(double x, double &z, double &a) {
+// c5 / c240 are the constants 5.0 and 240.0: v_fma_f64 takes one operand from the constant bus and neither is an inline
+// constant, so `fma(5.0, q, 240.0)` with two literals costs two moves per evaluation to put one of them into vector
+// registers.  A caller that evaluates this many times in a row passes values it holds in vector registers (made opaque
+// once, SplitConsts below).
+__device__ __forceinline__ void exp_digamma_split(double x, double c5, double c240, double &z, double &a) {
   const double q = x * (x + 9.0);
   double den = q + 60.0;
   den = fma(den, q, 1308.0);
   den = fma(den, q, 12176.0);
   den = fma(den, q, 40320.0);
   den *= q;
-  double num = fma(5.0, q, 240.0);
+  double num = fma(c5, q, c240);
   num = fma(num, q, 3924.0);
   num = fma(num, q, 24352.0);
   num = fma(num, q, 40320.0);
@@ -211,6 +215,7 @@ __device__ __forceinline__ void exp_digamma_split(double x, double &z, double &a
   t = fma(f, t, -0x1.5555555554867p-4);
   a = fma(rz, fma(rz, t, -0.5), -r);  // -1/(2z) + f P(f) - r
 }
+__device__ __forceinline__ void exp_digamma_split(double x, double &z, double &a) { exp_digamma_split(x, 5.0, 240.0, z, a); }
 
 // exp(d) for d <= 0 (the a_k - a_max above; also fine for moderate d > 0 -- nothing here depends on the sign, only
 // overflow is not handled): n = round(d / ln 2) taken from the low bits of d / ln 2 + 1.5 * 2^52 (no rounding and no
@@ -239,6 +244,19 @@ __device__ __forceinline__ double exp_nonpos(double d) {
   p = fma(p, r, 1.0);
   return __builtin_amdgcn_ldexp(p, (int)(uint32_t)__double_as_longlong(t));  // (2^-huge flushes to 0)
 }
+
+// The two constants of exp_digamma_split's `fma(5.0, q, 240.0)`, held in vector registers by a caller that evaluates it
+// many times in a row: opaque to the compiler, which would otherwise fold them back into literals and moves per
+// evaluation.  Same operation on the same values: the same bits.  (exp_nonpos's `fma(d, log2 e, kShift)` needs none of
+// this: the compiler keeps kShift in registers across a step by itself.)
+struct SplitConsts {
+  double c5, c240;
+  __device__ __forceinline__ void load() {
+    c5 = 5.0;
+    c240 = 240.0;
+    asm volatile("" : "+v"(c5), "+v"(c240));
+  }
+};
 
 // Cross-lane moves of the wave fold, all on the vector ALU (no trip through the LDS pipe):
 //  * pair_add<32|16>(a, b): v_permlane32_swap / v_permlane16_swap (gfx950) exchange the upper

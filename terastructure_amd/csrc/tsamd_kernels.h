@@ -100,8 +100,9 @@ __device__ __forceinline__ PendingIn load_pending(const State *S, uint32_t J) {
 }
 // The K x 2 epilogue proper, for the thread that holds lt = the row total of value j (threads j and j ^ 1 are
 // neighbouring lanes of one wave): lambda_t = eb_used * lt, update_lambda, estimate_beta; outputs into LDS.
+// (sc: the constants of exp_digamma_split's two-constant FMA, literals or a caller's registers -- SplitConsts, tsamd_device.h)
 __device__ __forceinline__ void epilogue_values_reg(const DevParams &p, uint32_t j, double lt, double eb_used, double lam_old,
-                                                    double &nw, double &eb_new, double &diff) {
+                                                    double &nw, double &eb_new, double &diff, const SplitConsts &sc) {
   // eta + b[k,t] * (row sum): the b factored out of the accumulation; an explicit fma so that
   // every kernel that inlines this rounds the same way whatever the compiler would contract
   nw = fma(lt, eb_used, (j & 1u) ? p.eta1 : p.eta0);
@@ -110,10 +111,14 @@ __device__ __forceinline__ void epilogue_values_reg(const DevParams &p, uint32_t
   // stream; the pair sum comes from the neighbouring lane (t = 0/1 are adjacent threads)
   const double pair = nw + partner<1>(nw);
   double z1, a1, z2, a2;
-  exp_digamma_split(nw, z1, a1);
-  exp_digamma_split(pair, z2, a2);
+  exp_digamma_split(nw, sc.c5, sc.c240, z1, a1);
+  exp_digamma_split(pair, sc.c5, sc.c240, z2, a2);
   eb_new = (z1 * fast_rcp(z2)) * exp_nonpos(a1 - a2);
   diff = fabs(nw - lam_old);
+}
+__device__ __forceinline__ void epilogue_values_reg(const DevParams &p, uint32_t j, double lt, double eb_used, double lam_old,
+                                                    double &nw, double &eb_new, double &diff) {
+  epilogue_values_reg(p, j, lt, eb_used, lam_old, nw, eb_new, diff, SplitConsts{5.0, 240.0});
 }
 __device__ __forceinline__ void epilogue_values_at(const DevParams &p, uint32_t j, double lt, double eb_used, double lam_old,
                                                    double *s_lam, double *s_eb, double *s_diff) {
@@ -379,16 +384,20 @@ __device__ __forceinline__ double row_partial_sum_xchg(const double *rows, uint3
 // src/snpsamplinge.cc:721-740).  The population with the largest a gets exp(0), so w never
 // underflows for all k at once.
 template <int KT>
-__device__ __forceinline__ void gamma_to_w(const double (&g)[KT], double (&w)[KT]) {
+__device__ __forceinline__ void gamma_to_w(const double (&g)[KT], double (&w)[KT], const SplitConsts &sc) {
   double z[KT], a[KT];
   double amax = -1.0e300;
 #pragma unroll
   for (int k = 0; k < KT; ++k) {
-    exp_digamma_split(g[k], z[k], a[k]);
+    exp_digamma_split(g[k], sc.c5, sc.c240, z[k], a[k]);
     amax = fmax(amax, a[k]);
   }
 #pragma unroll
   for (int k = 0; k < KT; ++k) w[k] = z[k] * exp_nonpos(a[k] - amax);
+}
+template <int KT>
+__device__ __forceinline__ void gamma_to_w(const double (&g)[KT], double (&w)[KT]) {
+  gamma_to_w<KT>(g, w, SplitConsts{5.0, 240.0});
 }
 
 // SVI step for one individual (update_gamma + update_rho_indiv,

@@ -956,6 +956,16 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
   // 72.7-73.0 against 73.6-74.0 us per update; until then it ran only below full size)
   constexpr bool kRepl = KT <= 8;
 #endif
+  // kDiet*: fewer vector instructions that compute nothing, the same bits (a lone wave pays 4.25 ... 4.7 cycles for every
+  // one, 16 for a select on vcc): the selects of the gamma step as arithmetic, and the constants of exp_digamma_split's
+  // two-constant FMA held in registers (SplitConsts).  K <= 8, where every instantiation has the registers for it; above,
+  // the kernel is as it was.  (Starting the accumulators with the sweep's first item instead of zero-filling them -- 32
+  // moves per pass -- was built with these and measured neutral: the moves issue in the shadow of the epilogue's
+  // dependent chain.  profiles/k8_instruction_diet.md)
+#ifndef TSAMD_DIET  // (experiments, tools/variant.sh: bit 0 the selects, bit 1 the constants)
+#define TSAMD_DIET 3
+#endif
+  constexpr bool kDietSel = KT <= 8 && (TSAMD_DIET & 1) != 0, kDietConst = KT <= 8 && (TSAMD_DIET & 2) != 0;
   __shared__ __attribute__((aligned(16))) double s_ebw[kWaves][J];
   __shared__ double s_diffw[kWaves][J];
   __shared__ double s_red[kWaves * J];
@@ -1245,9 +1255,11 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
 #endif
     if constexpr (kRepl) {
       const uint32_t lane = tid & 63u, wave = tid >> 6;
+      SplitConsts sc = {5.0, 240.0};
+      if constexpr (kDietConst) sc.load();
       if (lane < J) {
         double nw, ebn, df;
-        epilogue_values_reg(p, lane, res_total<KT, WR>(s_tot, lane), eb_used, lam_old, nw, ebn, df);
+        epilogue_values_reg(p, lane, res_total<KT, WR>(s_tot, lane), eb_used, lam_old, nw, ebn, df, sc);
         lam_old = nw;
         eb_used = ebn;
         if constexpr (!(BSC && TSAMD_REPL_READLANE)) s_ebw[wave][lane] = ebn;
@@ -1257,7 +1269,7 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
         if (blockIdx.x == 0) {  // the previous SNP's final epilogue and its publication: the second wave, from registers
           if (wave == 1u && lane < J) {
             double nw, ebn, df;
-            epilogue_values_reg(p, lane, res_total<KT, WR>(s_tot, J + lane), s_sb[lane], s_dlam[lane], nw, ebn, df);
+            epilogue_values_reg(p, lane, res_total<KT, WR>(s_tot, J + lane), s_sb[lane], s_dlam[lane], nw, ebn, df, sc);
             __hip_atomic_store(&p.lam[(size_t)dloc * J + lane], nw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&p.eb[(size_t)dloc * J + lane], ebn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -1354,6 +1366,8 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
 #pragma unroll
         for (int j = 0; j < (int)J; ++j) sbs[j] = lane_f64(eb_ran, j);
       }
+      SplitConsts sc = {5.0, 240.0};
+      if constexpr (kDietConst) sc.load();  // (in vector registers for the whole step: K evaluations per item use them)
       auto gamma_one = [&](double (&gx)[KT], double (&wx)[KT], uint32_t nib, uint32_t &cn) {
         const double mom = (double)(nib & 3u), dad = (double)((nib >> 2) & 3u);
         const bool ok = (nib & 15u) != 0u;  // (an observed genotype has y + (2 - y) = 2)
@@ -1371,7 +1385,10 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
           s0 = fma(wx[k], sb(2 * k), s0);
           s1 = fma(wx[k], sb(2 * k + 1), s1);
         }
-        const double rho = ok ? fast_rsqrt(p.nodetau0 + (double)cn) : 0.0;
+        // (kDietSel: the step size times exactly 1.0 or 0.0 -- x 1.0 keeps the bits, x 0.0 gives the +0 of the select)
+        const uint32_t oki = ((nib & 3u) + ((nib >> 2) & 3u)) >> 1;  // y + (2 - y) = 2 observed, 0 + 0 otherwise
+        double rho;
+        if constexpr (kDietSel) rho = fast_rsqrt(p.nodetau0 + (double)cn) * (double)oki; else rho = ok ? fast_rsqrt(p.nodetau0 + (double)cn) : 0.0;
         if constexpr (kLeanStep) {
           // gamma += rho (alpha + scale (y phi_mom + (2 - y) phi_dad) - gamma) as (1 - rho) gamma + rho alpha +
           // w_k (c0 sb0_k + c1 sb1_k) with rho * scale folded into c0 / c1 and ONE reciprocal (of s0 * s1) for both
@@ -1388,8 +1405,8 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
             gx[k] += rho * (p.alpha + p.gamma_scale * e - gx[k]);
           }
         }
-        if constexpr (KT <= 8) gamma_to_w<KT>(gx, wx); else gamma_to_w_lean<KT>(gx, wx);
-        cn = ok ? cn + 1u : cn;
+        if constexpr (kDietConst) gamma_to_w<KT>(gx, wx, sc); else if constexpr (KT <= 8) gamma_to_w<KT>(gx, wx); else gamma_to_w_lean<KT>(gx, wx);
+        if constexpr (kDietSel) cn += oki; else cn = ok ? cn + 1u : cn;
       };
       constexpr int kFirstStreamed = sched_next_streamed(-1, kLds, kItems);
       if (kFirstStreamed < kItems) load_gamma(item_or_last((uint32_t)kFirstStreamed), gs, cs);
