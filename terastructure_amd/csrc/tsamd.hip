@@ -90,6 +90,29 @@ struct GraphSlot {
   hipGraphExec_t exec = nullptr;
 };
 
+// Device scratch that a context keeps between calls: grows on demand, never shrinks, freed by tsamd_destroy.  A growth frees
+// the old block first and leaves the buffer empty when the allocation fails, so the context's next call tries again; the
+// caller sees to it that nothing in flight still uses the block (the analysis calls end with a synchronise).
+struct DevBuf {
+  void *ptr = nullptr;
+  size_t bytes = 0;
+  hipError_t reserve(size_t need) {
+    if (need <= bytes) return hipSuccess;
+    free();
+    const hipError_t e = hipMalloc(&ptr, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+  }
+  template <class T>
+  T *as() const {
+    return (T *)ptr;
+  }
+  void free() {
+    hipFree(ptr);
+    ptr = nullptr, bytes = 0;
+  }
+};
+
 }  // namespace
 
 struct tsamd_ctx {
@@ -104,51 +127,31 @@ struct tsamd_ctx {
   uint32_t sched_cap = 0;
   uint8_t *h_stage = nullptr;  // pinned staging for uploads
   size_t stage_bytes = 0;
-  double *d_state = nullptr;  // device staging of tsamd_state_export / _import (the individual part), kept between calls
-  size_t state_bytes = 0;
+  // device staging of tsamd_state_export / _import (the individual part): allocated by the first export or import and kept (a hipFree per
+  // call would synchronise the whole device, which other shards may share)
+  DevBuf d_state;
   std::map<uint32_t, HeldLoc> held;
   // flat device copy of the held-out table (ids + true genotypes, locations ascending), rebuilt
   // lazily after tsamd_set_heldout / a re-upload; spans index it by location
   bool held_dirty = true;
   std::map<uint32_t, std::pair<uint64_t, uint32_t>> held_span;
-  uint32_t *d_hids = nullptr;
-  uint8_t *d_hy = nullptr;
-  double *d_hterms = nullptr;
-  size_t held_cap = 0;
-  uint32_t *d_fold_ids = nullptr;  // scratch of tsamd_set_heldout
-  uint8_t *d_fold_orig = nullptr;
-  size_t fold_cap = 0;
-  HeldReq *d_hreq = nullptr;
-  double *d_hsums = nullptr;
-  size_t hreq_cap = 0;
-  // tsamd_train_loglik: partial-sum buffers (loglik_geometry: at most kLoglikScratchBound bytes), the chunk's locations and results, the
-  // call's per-individual accumulators and, at k > TSAMD_SPECIALIZED_K, the normalised theta; allocated on first use
-  void *d_ll_part = nullptr;
-  size_t ll_part_bytes = 0;
-  void *d_ll_chunk = nullptr;  // [chunk] locations, sums, counts
-  size_t ll_chunk_cap = 0;
-  void *d_ll_acc = nullptr;    // [npad] sums, [npad] counts
-  double *d_ll_thn = nullptr;  // [k][npad]
-  // tsamd_fold_in: the segments' partials (foldin_geometry: at most foldin_scratch_bound bytes), per individual the updates applied,
-  // the last change and the frozen flag, the active count and tile flags, the listed locations; allocated on first use
-  double *d_fi_part = nullptr;
-  size_t fi_part_bytes = 0;
-  void *d_fi_ind = nullptr;      // [npad] change, [npad] iters, [npad] frozen, [1 + npad / 256] active
-  uint32_t *d_fi_locs = nullptr;
-  size_t fi_locs_cap = 0;
+  DevBuf d_hids, d_hy, d_hterms;    // uint32_t, uint8_t, double per entry
+  DevBuf d_fold_ids, d_fold_orig;   // scratch of tsamd_set_heldout: uint32_t ids in, uint8_t codes out
+  DevBuf d_hreq, d_hsums;           // tsamd_heldout_eval: a HeldReq and a double per requested location
+  // tsamd_train_loglik: partial-sum buffers (loglik_geometry: at most kLoglikScratchBound bytes), the chunk's results and locations
+  // ([cap] sums, counts, locations: cap = the bytes / kLoglikChunkRow), the call's per-individual accumulators ([npad] sums, counts)
+  // and, at k > TSAMD_SPECIALIZED_K, the normalised theta [k][npad] (runtime_k_theta: tsamd_snp_scan's too); allocated on first use
+  DevBuf d_ll_part, d_ll_chunk, d_ll_acc, d_ll_thn;
+  // tsamd_fold_in: the segments' partials (foldin_geometry: at most foldin_scratch_bound bytes), per individual the last change, the
+  // updates applied and the frozen flag, then the active count and tile flags ([npad] change, iters, frozen, [1 + npad / 256] active),
+  // the listed locations; allocated on first use
+  DevBuf d_fi_part, d_fi_ind, d_fi_locs;
   // tsamd_kinship: r and s of a chunk, the segments' partial tiles (kin_geometry: at most kKinScratchBound bytes each), the call's
-  // two [mpad][mpad] accumulators, the listed individuals' rows and the chunk's locations; allocated on first use
-  double *d_kin_rs = nullptr, *d_kin_part = nullptr, *d_kin_acc = nullptr;
-  size_t kin_rs_bytes = 0, kin_part_bytes = 0, kin_acc_bytes = 0;
-  uint32_t *d_kin_idx = nullptr;  // [mpad] rows, then [chunk] locations
-  size_t kin_idx_cap = 0;
-  // tsamd_snp_scan: the tiles' partials (scan_geometry: at most kScanScratchBound bytes), the chunk's locations and rows, the trait
-  // padded to npad; allocated on first use
-  double *d_scan_part = nullptr;
-  size_t scan_part_bytes = 0;
-  void *d_scan_chunk = nullptr;  // [chunk][10] sums, [chunk][4] counts, [chunk] locations
-  size_t scan_chunk_cap = 0;
-  double *d_scan_trait = nullptr;  // [npad]
+  // two [mpad][mpad] accumulators, the listed individuals' rows [mpad] and then the chunk's locations; allocated on first use
+  DevBuf d_kin_rs, d_kin_part, d_kin_acc, d_kin_idx;
+  // tsamd_snp_scan: the tiles' partials (scan_geometry: at most kScanScratchBound bytes), the chunk's rows and locations ([cap][10] sums,
+  // [cap][4] counts, [cap] locations: cap = the bytes / kScanChunkRow), the trait padded to npad; allocated on first use
+  DevBuf d_scan_part, d_scan_chunk, d_scan_trait;
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -428,6 +431,10 @@ uint32_t env_u32(const char *name, uint32_t dflt) {
   return (s && *s) ? (uint32_t)std::max(0, atoi(s)) : dflt;
 }
 
+// A TSAMD_TEST_* hook, read when it is asked for: 0 unless the context was created with TSAMD_FLAG_TEST_HOOKS -- a stray
+// environment variable must never reshape a production run
+uint32_t test_hook(const tsamd_ctx *c, const char *name) { return (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u ? env_u32(name, 0) : 0u; }
+
 // The environment variables that shape the launch plan, read here and nowhere else: at context creation, when an exchange
 // is activated and for the geometry of a recovery.  (TSAMD_HOLBLOCK and TSAMD_SINGLE_ROUTE are read per call.)
 Knobs read_knobs() {
@@ -555,6 +562,62 @@ int check_locs(tsamd_ctx *c, uint32_t first_loc, uint32_t n_locs) {
   return TSAMD_OK;
 }
 
+// ---- the front end of the analysis calls: tsamd_train_loglik, tsamd_fold_in, tsamd_kinship, tsamd_snp_scan ---------------------
+
+// the list of locations such a call takes (locs == NULL: locations 0 .. n_locs - 1)
+int check_loc_list(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs) {
+  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
+  if (locs)
+    for (uint32_t i = 0; i < n_locs; ++i)
+      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  return TSAMD_OK;
+}
+
+// compute units such a call fills: the device's, or fewer under TSAMD_TEST_MAX_WORKGROUPS (a test-hooks context only)
+uint32_t device_width(const tsamd_ctx *c) {
+  const uint32_t cus = (uint32_t)std::max(1, c->in.cus);
+  const uint32_t cap = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u ? c->in.knobs.test_max_workgroups : 0u;
+  return cap > 0u ? std::min(cus, cap) : cus;
+}
+
+// run-time-K path (k > TSAMD_SPECIALIZED_K) of train_loglik and snp_scan: the normalised theta of the gamma as it stands, in
+// scratch allocated on first use; *thn stays NULL at a specialised K
+int runtime_k_theta(tsamd_ctx *c, const double **thn) {
+  *thn = nullptr;
+  if (c->cfg.k <= (uint32_t)TSAMD_SPECIALIZED_K) return TSAMD_OK;
+  HIP_TRY(c, c->d_ll_thn.reserve((size_t)c->cfg.k * c->npad * sizeof(double)));
+  loglik_launch_theta(c->p.gam, c->npad, c->cfg.k, c->d_ll_thn.as<double>(), c->stream);
+  *thn = c->d_ll_thn.as<double>();
+  return TSAMD_OK;
+}
+
+// The chunk loop of train_loglik, kinship and snp_scan.  The listed locations go chunk after chunk: a chunk's locations are
+// staged and uploaded to d_locs, enqueue(len) launches its kernels, its results -- row_bytes per listed location from dev to
+// host, for each of outs -- are fetched, the stream is waited for (the staging vector and the hosts' buffers are reused) and
+// collect(off, len) takes the results, so in listed order.
+struct ChunkOut {
+  void *host;
+  const void *dev;
+  size_t row_bytes;
+};
+template <class Enqueue, class Collect>
+int for_each_chunk(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t chunk, uint32_t *d_locs, std::initializer_list<ChunkOut> outs,
+                   Enqueue enqueue, Collect collect) {
+  std::vector<uint32_t> h_locs(chunk);
+  for (uint32_t off = 0; off < n_locs; off += chunk) {
+    const uint32_t len = std::min(chunk, n_locs - off);
+    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
+    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    enqueue(len);
+    HIP_TRY(c, hipGetLastError());
+    for (const ChunkOut &o : outs) HIP_TRY(c, hipMemcpyAsync(o.host, o.dev, (size_t)len * o.row_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    collect(off, len);
+  }
+  return TSAMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -623,29 +686,12 @@ void tsamd_destroy(tsamd_ctx *c) {
     hipStreamDestroy(c->aux_stream);
   }
   if (c->h_occupy) hipHostFree(c->h_occupy);
-  hipFree(c->d_hids);
-  hipFree(c->d_hy);
-  hipFree(c->d_hterms);
-  hipFree(c->d_hreq);
-  hipFree(c->d_fold_ids);
-  hipFree(c->d_fold_orig);
-  hipFree(c->d_hsums);
-  hipFree(c->d_ll_part);
-  hipFree(c->d_ll_chunk);
-  hipFree(c->d_ll_acc);
-  hipFree(c->d_ll_thn);
-  hipFree(c->d_fi_part);
-  hipFree(c->d_fi_ind);
-  hipFree(c->d_fi_locs);
-  hipFree(c->d_kin_rs);
-  hipFree(c->d_kin_part);
-  hipFree(c->d_kin_acc);
-  hipFree(c->d_kin_idx);
-  hipFree(c->d_scan_part);
-  hipFree(c->d_scan_chunk);
-  hipFree(c->d_scan_trait);
+  for (DevBuf *b : {&c->d_hids, &c->d_hy, &c->d_hterms, &c->d_hreq, &c->d_fold_ids, &c->d_fold_orig, &c->d_hsums, &c->d_ll_part, &c->d_ll_chunk,
+                    &c->d_ll_acc, &c->d_ll_thn, &c->d_fi_part, &c->d_fi_ind, &c->d_fi_locs, &c->d_kin_rs, &c->d_kin_part, &c->d_kin_acc,
+                    &c->d_kin_idx, &c->d_scan_part, &c->d_scan_chunk, &c->d_scan_trait})
+    b->free();
   if (c->h_stage) hipHostFree(c->h_stage);
-  hipFree(c->d_state);
+  c->d_state.free();
   for (auto &j : c->journal) {
     hipHostFree(j.ent);
     if (j.done) hipEventDestroy(j.done);
@@ -992,21 +1038,13 @@ int tsamd_set_heldout(tsamd_ctx *c, uint32_t loc, const uint32_t *indivs, uint32
   }
   HIP_TRY(c, hipSetDevice(c->dev));
   // persistent scratch (ids in, original 2-bit codes out): no allocation per call
-  if (ids.size() > c->fold_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipFree(c->d_fold_ids);
-    hipFree(c->d_fold_orig);
-    c->d_fold_ids = nullptr;
-    c->d_fold_orig = nullptr;
-    c->fold_cap = 0;
-    size_t cap = 4096;
-    while (cap < ids.size()) cap *= 2;
-    HIP_TRY(c, hipMalloc((void **)&c->d_fold_ids, cap * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_fold_orig, cap));
-    c->fold_cap = cap;
-  }
-  uint32_t *d_ids = c->d_fold_ids;
-  uint8_t *d_orig = c->d_fold_orig;
+  size_t cap = 4096;
+  while (cap < ids.size()) cap *= 2;
+  if (cap * sizeof(uint32_t) > c->d_fold_ids.bytes || cap > c->d_fold_orig.bytes) HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a growth frees)
+  HIP_TRY(c, c->d_fold_ids.reserve(cap * sizeof(uint32_t)));
+  HIP_TRY(c, c->d_fold_orig.reserve(cap));
+  uint32_t *d_ids = c->d_fold_ids.as<uint32_t>();
+  uint8_t *d_orig = c->d_fold_orig.as<uint8_t>();
   std::vector<uint8_t> orig(ids.size());
   hipError_t e = hipMemcpyAsync(d_ids, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -1610,19 +1648,12 @@ static int sync_held_table(tsamd_ctx *c) {
     ys.insert(ys.end(), kv.second.ytrue.begin(), kv.second.ytrue.end());
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (total > c->held_cap) {
-    hipFree(c->d_hids);
-    hipFree(c->d_hy);
-    hipFree(c->d_hterms);
-    c->d_hids = nullptr, c->d_hy = nullptr, c->d_hterms = nullptr, c->held_cap = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_hids, total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_hy, total));
-    HIP_TRY(c, hipMalloc((void **)&c->d_hterms, total * sizeof(double)));
-    c->held_cap = total;
-  }
+  HIP_TRY(c, c->d_hids.reserve(total * sizeof(uint32_t)));
+  HIP_TRY(c, c->d_hy.reserve(total));
+  HIP_TRY(c, c->d_hterms.reserve(total * sizeof(double)));
   if (total) {
-    HIP_TRY(c, hipMemcpy(c->d_hids, ids.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_hy, ys.data(), total, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_hids.ptr, ids.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_hy.ptr, ys.data(), total, hipMemcpyHostToDevice));
   }
   c->held_dirty = false;
   return TSAMD_OK;
@@ -1652,20 +1683,14 @@ int tsamd_heldout_eval(tsamd_ctx *c, const uint32_t *locs, uint32_t n, int run_u
   }
   std::vector<double> sums(req.size(), 0.0);
   if (!req.empty()) {
-    if (req.size() > c->hreq_cap) {
-      hipFree(c->d_hreq);
-      hipFree(c->d_hsums);
-      c->d_hreq = nullptr, c->d_hsums = nullptr, c->hreq_cap = 0;
-      size_t cap = 64;
-      while (cap < req.size()) cap *= 2;
-      HIP_TRY(c, hipMalloc((void **)&c->d_hreq, cap * sizeof(HeldReq)));
-      HIP_TRY(c, hipMalloc((void **)&c->d_hsums, cap * sizeof(double)));
-      c->hreq_cap = cap;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_hreq, req.data(), req.size() * sizeof(HeldReq), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(ts_heldout_eval, dim3((uint32_t)req.size()), dim3(256), 0, c->stream, c->p.gam, c->npad, c->cfg.k,
-                       c->p.lam, c->d_hids, c->d_hy, c->d_hreq, c->d_hterms, c->d_hsums);
-    HIP_TRY(c, hipMemcpyAsync(sums.data(), c->d_hsums, req.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    size_t cap = 64;
+    while (cap < req.size()) cap *= 2;
+    HIP_TRY(c, c->d_hreq.reserve(cap * sizeof(HeldReq)));
+    HIP_TRY(c, c->d_hsums.reserve(cap * sizeof(double)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_hreq.ptr, req.data(), req.size() * sizeof(HeldReq), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(ts_heldout_eval, dim3((uint32_t)req.size()), dim3(256), 0, c->stream, c->p.gam, c->npad, c->cfg.k, c->p.lam,
+                       c->d_hids.as<uint32_t>(), c->d_hy.as<uint8_t>(), c->d_hreq.as<HeldReq>(), c->d_hterms.as<double>(), c->d_hsums.as<double>());
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), c->d_hsums.ptr, req.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   double s = 0.0;
@@ -1694,71 +1719,53 @@ int tsamd_train_loglik(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, doub
   CHECK_CTX(c);
   if (sum) *sum = 0.0;
   if (count) *count = 0;
-  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
-  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
-  if (locs)
-    for (uint32_t i = 0; i < n_locs; ++i)
-      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
   HIP_TRY(c, hipSetDevice(c->dev));
   SETTLE(c);
-  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
-  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
-  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
   const uint32_t K = c->cfg.k, np = c->npad;
-  const LoglikGeom g = loglik_geometry(np, K, cus, hooks ? env_u32("TSAMD_TEST_LOGLIK_CHUNK", 0) : 0u);
+  const LoglikGeom g = loglik_geometry(np, K, device_width(c), test_hook(c, "TSAMD_TEST_LOGLIK_CHUNK"));
   const uint32_t chunk = std::min(g.chunk, n_locs);
 
   const size_t part_loc = (size_t)chunk * g.ntiles, part_ind = (size_t)g.nseg_max * np;
-  const size_t part_bytes = (part_loc + part_ind) * kLoglikPartBytes;
-  if (part_bytes > c->ll_part_bytes) {
-    hipFree(c->d_ll_part);
-    c->d_ll_part = nullptr, c->ll_part_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->d_ll_part, part_bytes));
-    c->ll_part_bytes = part_bytes;
-  }
-  if (chunk > c->ll_chunk_cap) {
-    hipFree(c->d_ll_chunk);
-    c->d_ll_chunk = nullptr, c->ll_chunk_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_ll_chunk, (size_t)chunk * 16));
-    c->ll_chunk_cap = chunk;
-  }
-  if (!c->d_ll_acc) HIP_TRY(c, hipMalloc(&c->d_ll_acc, (size_t)np * kLoglikPartBytes));
-  if (K > (uint32_t)TSAMD_SPECIALIZED_K && !c->d_ll_thn) HIP_TRY(c, hipMalloc((void **)&c->d_ll_thn, (size_t)K * np * sizeof(double)));
+  constexpr size_t kLoglikChunkRow = sizeof(double) + 2 * sizeof(uint32_t);  // a listed location's sum, count and location
+  HIP_TRY(c, c->d_ll_part.reserve((part_loc + part_ind) * kLoglikPartBytes));
+  HIP_TRY(c, c->d_ll_chunk.reserve((size_t)chunk * kLoglikChunkRow));
+  HIP_TRY(c, c->d_ll_acc.reserve((size_t)np * kLoglikPartBytes));
+  const size_t cap = c->d_ll_chunk.bytes / kLoglikChunkRow;
   // (the doubles first: every array starts on a multiple of 8 bytes)
-  double *part_loc_sum = (double *)c->d_ll_part, *part_ind_sum = part_loc_sum + part_loc;
+  double *part_loc_sum = c->d_ll_part.as<double>(), *part_ind_sum = part_loc_sum + part_loc;
   uint32_t *part_loc_cnt = (uint32_t *)(part_ind_sum + part_ind), *part_ind_cnt = part_loc_cnt + part_loc;
-  double *d_sum = (double *)c->d_ll_chunk;
-  uint32_t *d_cnt = (uint32_t *)(d_sum + c->ll_chunk_cap), *d_locs = d_cnt + c->ll_chunk_cap;
-  double *acc_sum = (double *)c->d_ll_acc;
+  double *d_sum = c->d_ll_chunk.as<double>();
+  uint32_t *d_cnt = (uint32_t *)(d_sum + cap), *d_locs = d_cnt + cap;
+  double *acc_sum = c->d_ll_acc.as<double>();
   uint32_t *acc_cnt = (uint32_t *)(acc_sum + np);
 
-  HIP_TRY(c, hipMemsetAsync(c->d_ll_acc, 0, (size_t)np * kLoglikPartBytes, c->stream));
-  if (c->d_ll_thn) loglik_launch_theta(c->p.gam, np, K, c->d_ll_thn, c->stream);
-  std::vector<uint32_t> h_locs(chunk), h_cnt(chunk);
+  HIP_TRY(c, hipMemsetAsync(acc_sum, 0, (size_t)np * kLoglikPartBytes, c->stream));
+  LoglikArgs a{};
+  if (int rc = runtime_k_theta(c, &a.thn)) return rc;
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam, a.locs = d_locs;
+  a.npad = np, a.K = K, a.ntiles = g.ntiles;
+  a.part_loc_sum = part_loc_sum, a.part_loc_cnt = part_loc_cnt, a.part_ind_sum = part_ind_sum, a.part_ind_cnt = part_ind_cnt;
+  std::vector<uint32_t> h_cnt(chunk);
   std::vector<double> h_sum(chunk);
   double total = 0.0;
   uint64_t total_cnt = 0;
-  for (uint32_t off = 0; off < n_locs; off += chunk) {
-    const uint32_t len = std::min(chunk, n_locs - off);
-    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
-    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    const LoglikSegs sg = loglik_segments(g, len);
-    LoglikArgs a{};
-    a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.thn = c->d_ll_thn, a.lam = c->p.lam, a.locs = d_locs;
-    a.npad = np, a.K = K, a.len = len, a.seg_len = sg.seg_len, a.ntiles = g.ntiles;
-    a.part_loc_sum = part_loc_sum, a.part_loc_cnt = part_loc_cnt, a.part_ind_sum = part_ind_sum, a.part_ind_cnt = part_ind_cnt;
-    loglik_launch_chunk(a, sg.nseg, d_sum, d_cnt, acc_sum, acc_cnt, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(h_sum.data(), d_sum, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < len; ++i) {  // listed order
-      if (loc_sums) loc_sums[off + i] = h_sum[i];
-      if (loc_counts) loc_counts[off + i] = h_cnt[i];
-      total += h_sum[i];
-      total_cnt += h_cnt[i];
-    }
-  }
+  const int rc = for_each_chunk(
+      c, locs, n_locs, chunk, d_locs, {{h_sum.data(), d_sum, sizeof(double)}, {h_cnt.data(), d_cnt, sizeof(uint32_t)}},
+      [&](uint32_t len) {
+        const LoglikSegs sg = loglik_segments(g, len);
+        a.len = len, a.seg_len = sg.seg_len;
+        loglik_launch_chunk(a, sg.nseg, d_sum, d_cnt, acc_sum, acc_cnt, c->stream);
+      },
+      [&](uint32_t off, uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i) {
+          if (loc_sums) loc_sums[off + i] = h_sum[i];
+          if (loc_counts) loc_counts[off + i] = h_cnt[i];
+          total += h_sum[i];
+          total_cnt += h_cnt[i];
+        }
+      });
+  if (rc) return rc;
   if (indiv_sums) HIP_TRY(c, hipMemcpyAsync(indiv_sums, acc_sum, (size_t)c->n_local * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (indiv_counts) HIP_TRY(c, hipMemcpyAsync(indiv_counts, acc_cnt, (size_t)c->n_local * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1773,42 +1780,27 @@ int tsamd_fold_in(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t 
   CHECK_CTX(c);
   if (n_converged) *n_converged = 0;
   if (iters_run) *iters_run = 0;
-  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (n_locs == 0) return check_loc_list(c, locs, n_locs);  // (the order of the checks is part of the behaviour)
   if (max_iters == 0) return fail(c, TSAMD_EINVAL, "max_iters must be positive");
   if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(c, TSAMD_EINVAL, "tol must be finite and not negative");
-  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
-  if (locs)
-    for (uint32_t i = 0; i < n_locs; ++i)
-      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
   HIP_TRY(c, hipSetDevice(c->dev));
   SETTLE(c);
-  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
-  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
-  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
   const uint32_t K = c->cfg.k, np = c->npad;
-  const FoldinGeom g = foldin_geometry(np, K, n_locs, cus, hooks ? env_u32("TSAMD_TEST_FOLDIN_SEGMENTS", 0) : 0u);
+  const FoldinGeom g = foldin_geometry(np, K, n_locs, device_width(c), test_hook(c, "TSAMD_TEST_FOLDIN_SEGMENTS"));
 
-  const size_t part_bytes = (size_t)foldin_scratch_bytes(g, np, K);
-  if (part_bytes > c->fi_part_bytes) {
-    hipFree(c->d_fi_part);
-    c->d_fi_part = nullptr, c->fi_part_bytes = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_fi_part, part_bytes));
-    c->fi_part_bytes = part_bytes;
-  }
+  HIP_TRY(c, c->d_fi_part.reserve((size_t)foldin_scratch_bytes(g, np, K)));
   const size_t max_tiles = np / kFoldinBlock;  // (the smallest tile)
-  if (!c->d_fi_ind) HIP_TRY(c, hipMalloc(&c->d_fi_ind, (size_t)np * 16 + (1 + max_tiles) * sizeof(uint32_t)));
-  if (locs && n_locs > c->fi_locs_cap) {
-    hipFree(c->d_fi_locs);
-    c->d_fi_locs = nullptr, c->fi_locs_cap = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_fi_locs, (size_t)n_locs * sizeof(uint32_t)));
-    c->fi_locs_cap = n_locs;
+  HIP_TRY(c, c->d_fi_ind.reserve((size_t)np * 16 + (1 + max_tiles) * sizeof(uint32_t)));
+  if (locs) {
+    HIP_TRY(c, c->d_fi_locs.reserve((size_t)n_locs * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_fi_locs.ptr, locs, (size_t)n_locs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   }
-  if (locs) HIP_TRY(c, hipMemcpyAsync(c->d_fi_locs, locs, (size_t)n_locs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 
   FoldinArgs a{};
-  a.bed = c->p.bed, a.colstride = c->p.colstride, a.eb = c->p.eb, a.locs = locs ? c->d_fi_locs : nullptr;
-  a.gam = c->p.gam, a.w = c->p.w, a.part = c->d_fi_part;
-  a.change = (double *)c->d_fi_ind;  // (the doubles first: every array starts on a multiple of 8 bytes)
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.eb = c->p.eb, a.locs = locs ? c->d_fi_locs.as<uint32_t>() : nullptr;
+  a.gam = c->p.gam, a.w = c->p.w, a.part = c->d_fi_part.as<double>();
+  a.change = c->d_fi_ind.as<double>();  // (the doubles first: every array starts on a multiple of 8 bytes)
   a.iters = (uint32_t *)(a.change + np), a.frozen = a.iters + np, a.active = a.frozen + np;
   a.npad = np, a.n_local = c->n_local, a.K = K, a.n_locs = n_locs, a.nseg = g.nseg, a.seg_len = g.seg_len, a.ntiles = g.ntiles, a.tile_n = g.tile_n;
   a.alpha = c->p.alpha, a.tol = tol;
@@ -1850,12 +1842,9 @@ int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32
   CHECK_CTX(c);
   if (m == 0) return fail(c, TSAMD_EINVAL, "m must be positive");
   if (m > TSAMD_KIN_MAX_M) return fail(c, TSAMD_EINVAL, "m = %u exceeds TSAMD_KIN_MAX_M = %u", m, (uint32_t)TSAMD_KIN_MAX_M);
-  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (n_locs == 0) return check_loc_list(c, locs, n_locs);
   if (!kin && !num && !den) return fail(c, TSAMD_EINVAL, "kin, num and den are all NULL");
-  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
-  if (locs)
-    for (uint32_t i = 0; i < n_locs; ++i)
-      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
   if (!indivs && m > c->n_local) return fail(c, TSAMD_EINVAL, "m = %u exceeds the shard's %u individuals (indivs == NULL: its first m)", m, c->n_local);
   if (indivs)
     for (uint32_t i = 0; i < m; ++i)
@@ -1863,36 +1852,20 @@ int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32
         return fail(c, TSAMD_EINVAL, "indivs[%u] = %u is outside the shard [%u, %u)", i, indivs[i], c->n_begin, c->n_begin + c->n_local);
   HIP_TRY(c, hipSetDevice(c->dev));
   SETTLE(c);
-  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
-  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
-  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
   static_assert(TSAMD_KIN_MAX_M == kKinMaxM, "the header's bound is the plan's");
-  KinGeom g = kin_geometry(m, cus, hooks ? env_u32("TSAMD_TEST_KIN_CHUNK", 0) : 0u, hooks ? env_u32("TSAMD_TEST_KIN_SEGMENTS", 0) : 0u);
+  KinGeom g = kin_geometry(m, device_width(c), test_hook(c, "TSAMD_TEST_KIN_CHUNK"), test_hook(c, "TSAMD_TEST_KIN_SEGMENTS"));
   g.chunk = std::min(g.chunk, n_locs);
   const uint32_t chunk4 = kin_round_step(g.chunk);
 
-  auto grow = [&](double **p, size_t *have, size_t need) -> hipError_t {
-    if (need <= *have) return hipSuccess;
-    hipFree(*p);
-    *p = nullptr, *have = 0;
-    hipError_t e = hipMalloc((void **)p, need);
-    if (e == hipSuccess) *have = need;
-    return e;
-  };
-  HIP_TRY(c, grow(&c->d_kin_rs, &c->kin_rs_bytes, (size_t)kin_rs_bytes(g)));
-  HIP_TRY(c, grow(&c->d_kin_part, &c->kin_part_bytes, (size_t)kin_part_bytes(g)));
-  HIP_TRY(c, grow(&c->d_kin_acc, &c->kin_acc_bytes, (size_t)kin_acc_bytes(g)));
-  if ((size_t)g.mpad + g.chunk > c->kin_idx_cap) {
-    hipFree(c->d_kin_idx);
-    c->d_kin_idx = nullptr, c->kin_idx_cap = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_kin_idx, ((size_t)g.mpad + g.chunk) * sizeof(uint32_t)));
-    c->kin_idx_cap = (size_t)g.mpad + g.chunk;
-  }
-  uint32_t *d_ids = c->d_kin_idx, *d_locs = d_ids + g.mpad;
+  HIP_TRY(c, c->d_kin_rs.reserve((size_t)kin_rs_bytes(g)));
+  HIP_TRY(c, c->d_kin_part.reserve((size_t)kin_part_bytes(g)));
+  HIP_TRY(c, c->d_kin_acc.reserve((size_t)kin_acc_bytes(g)));
+  HIP_TRY(c, c->d_kin_idx.reserve(((size_t)g.mpad + g.chunk) * sizeof(uint32_t)));
+  uint32_t *d_ids = c->d_kin_idx.as<uint32_t>(), *d_locs = d_ids + g.mpad;
   const size_t mm = (size_t)g.mpad * g.mpad;
-  double *d_num = c->d_kin_acc, *d_den = d_num + mm;
+  double *d_num = c->d_kin_acc.as<double>(), *d_den = d_num + mm;
 
-  std::vector<uint32_t> h_ids(g.mpad, 0xffffffffu), h_locs(g.chunk);
+  std::vector<uint32_t> h_ids(g.mpad, 0xffffffffu);
   for (uint32_t i = 0; i < m; ++i) h_ids[i] = indivs ? indivs[i] - c->n_begin : i;
   HIP_TRY(c, hipMemcpyAsync(d_ids, h_ids.data(), (size_t)g.mpad * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemsetAsync(d_num, 0, 2 * mm * sizeof(double), c->stream));
@@ -1900,19 +1873,18 @@ int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32
   KinArgs a{};
   a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam, a.ids = d_ids, a.locs = d_locs;
   a.npad = c->npad, a.K = c->cfg.k, a.mpad = g.mpad, a.ntiles = g.ntiles;
-  a.r = c->d_kin_rs, a.s = a.r + (size_t)chunk4 * g.mpad, a.part = c->d_kin_part, a.num = d_num, a.den = d_den;
-  for (uint32_t off = 0; off < n_locs; off += g.chunk) {
-    const uint32_t len = std::min(g.chunk, n_locs - off);
-    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
-    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    a.len = len, a.len4 = kin_round_step(len);
-    const KinSegs sg = kin_segments(g, len);
-    kin_launch_resid(a, c->stream);
-    for (uint32_t p0 = 0; p0 < g.npairs; p0 += g.pairs_per_launch)
-      kin_launch_pairs(a, p0, std::min(g.pairs_per_launch, g.npairs - p0), sg, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (h_locs is reused)
-  }
+  a.r = c->d_kin_rs.as<double>(), a.s = a.r + (size_t)chunk4 * g.mpad, a.part = c->d_kin_part.as<double>(), a.num = d_num, a.den = d_den;
+  const int rc = for_each_chunk(
+      c, locs, n_locs, g.chunk, d_locs, {},
+      [&](uint32_t len) {
+        a.len = len, a.len4 = kin_round_step(len);
+        const KinSegs sg = kin_segments(g, len);
+        kin_launch_resid(a, c->stream);
+        for (uint32_t p0 = 0; p0 < g.npairs; p0 += g.pairs_per_launch)
+          kin_launch_pairs(a, p0, std::min(g.pairs_per_launch, g.npairs - p0), sg, c->stream);
+      },
+      [](uint32_t, uint32_t) {});  // (the accumulators stay on the device until the last chunk)
+  if (rc) return rc;
   kin_launch_mirror(d_num, d_den, g.mpad, c->stream);
   HIP_TRY(c, hipGetLastError());
   auto fetch = [&](double *dst, const double *src) {
@@ -1937,80 +1909,61 @@ int tsamd_snp_scan(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, const do
   static_assert(TSAMD_SCAN_FIT_SUMS == kScanFitSums && TSAMD_SCAN_FIT_COUNTS == kScanFitCounts && TSAMD_SCAN_TRAIT_SUMS == kScanTraitSums &&
                     TSAMD_SCAN_STATS == kScanStats,
                 "the header's row lengths are the plan's");
-  if (n_locs == 0) return fail(c, TSAMD_EINVAL, "n_locs must be positive");
+  if (n_locs == 0) return check_loc_list(c, locs, n_locs);
   if (!fit_sums && !fit_counts && !trait_sums && !trait_counts)
     return fail(c, TSAMD_EINVAL, "fit_sums, fit_counts, trait_sums and trait_counts are all NULL");
   if (!trait && (trait_sums || trait_counts)) return fail(c, TSAMD_EINVAL, "trait_sums / trait_counts requested without a trait");
   if (trait && !trait_sums && !trait_counts) return fail(c, TSAMD_EINVAL, "a trait is given but trait_sums and trait_counts are both NULL");
-  if (!locs && n_locs > c->cfg.l) return fail(c, TSAMD_EINVAL, "n_locs = %u exceeds l = %u (locs == NULL: locations 0 .. n_locs-1)", n_locs, c->cfg.l);
-  if (locs)
-    for (uint32_t i = 0; i < n_locs; ++i)
-      if (locs[i] >= c->cfg.l) return fail(c, TSAMD_EINVAL, "locs[%u] = %u is not a location (l = %u)", i, locs[i], c->cfg.l);
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
   if (trait)
     for (uint32_t i = 0; i < c->n_local; ++i)
       if (std::isinf(trait[i])) return fail(c, TSAMD_EINVAL, "trait[%u] is infinite (NaN marks an individual without a trait value)", i);
   HIP_TRY(c, hipSetDevice(c->dev));
   SETTLE(c);
-  const bool hooks = (c->cfg.flags & TSAMD_FLAG_TEST_HOOKS) != 0u;
-  uint32_t cus = (uint32_t)std::max(1, c->in.cus);
-  if (hooks && c->in.knobs.test_max_workgroups > 0u) cus = std::min(cus, c->in.knobs.test_max_workgroups);
   const uint32_t K = c->cfg.k, np = c->npad;
-  ScanGeom g = scan_geometry(np, K, trait != nullptr, cus, hooks ? env_u32("TSAMD_TEST_SCAN_CHUNK", 0) : 0u);
+  ScanGeom g = scan_geometry(np, K, trait != nullptr, device_width(c), test_hook(c, "TSAMD_TEST_SCAN_CHUNK"));
   g.chunk = std::min(g.chunk, n_locs);
 
-  const size_t part_bytes = (size_t)scan_scratch_bytes(g);
-  if (part_bytes > c->scan_part_bytes) {
-    hipFree(c->d_scan_part);
-    c->d_scan_part = nullptr, c->scan_part_bytes = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_scan_part, part_bytes));
-    c->scan_part_bytes = part_bytes;
-  }
   constexpr size_t kRowSums = kScanFitSums + kScanTraitSums, kRowCounts = kScanFitCounts + 1;
-  if (g.chunk > c->scan_chunk_cap) {
-    hipFree(c->d_scan_chunk);
-    c->d_scan_chunk = nullptr, c->scan_chunk_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_scan_chunk, (size_t)g.chunk * (kRowSums * sizeof(double) + (kRowCounts + 1) * sizeof(uint32_t))));
-    c->scan_chunk_cap = g.chunk;
-  }
-  if (trait && !c->d_scan_trait) HIP_TRY(c, hipMalloc((void **)&c->d_scan_trait, (size_t)np * sizeof(double)));
-  if (K > (uint32_t)TSAMD_SPECIALIZED_K && !c->d_ll_thn) HIP_TRY(c, hipMalloc((void **)&c->d_ll_thn, (size_t)K * np * sizeof(double)));
+  constexpr size_t kScanChunkRow = kRowSums * sizeof(double) + (kRowCounts + 1) * sizeof(uint32_t);  // a listed location's sums, counts and location
+  HIP_TRY(c, c->d_scan_part.reserve((size_t)scan_scratch_bytes(g)));
+  HIP_TRY(c, c->d_scan_chunk.reserve((size_t)g.chunk * kScanChunkRow));
+  if (trait) HIP_TRY(c, c->d_scan_trait.reserve((size_t)np * sizeof(double)));
+  const size_t cap = c->d_scan_chunk.bytes / kScanChunkRow;
   // (the doubles first: every array starts on a multiple of 8 bytes)
-  double *d_sums = (double *)c->d_scan_chunk;
-  uint32_t *d_counts = (uint32_t *)(d_sums + c->scan_chunk_cap * kRowSums), *d_locs = d_counts + c->scan_chunk_cap * kRowCounts;
+  double *d_sums = c->d_scan_chunk.as<double>();
+  uint32_t *d_counts = (uint32_t *)(d_sums + cap * kRowSums), *d_locs = d_counts + cap * kRowCounts;
 
   std::vector<double> h_trait;
   if (trait) {  // padding individuals carry no trait value
     h_trait.assign(np, std::numeric_limits<double>::quiet_NaN());
     std::copy(trait, trait + c->n_local, h_trait.begin());
-    HIP_TRY(c, hipMemcpyAsync(c->d_scan_trait, h_trait.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_scan_trait.ptr, h_trait.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  if (K > (uint32_t)TSAMD_SPECIALIZED_K) loglik_launch_theta(c->p.gam, np, K, c->d_ll_thn, c->stream);
-  std::vector<uint32_t> h_locs(g.chunk), h_counts((size_t)g.chunk * kRowCounts);
+  ScanArgs a{};
+  if (int rc = runtime_k_theta(c, &a.thn)) return rc;
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam;
+  a.trait = trait ? c->d_scan_trait.as<double>() : nullptr, a.locs = d_locs;
+  a.npad = np, a.K = K, a.ntiles = g.ntiles, a.part = c->d_scan_part.as<double>();
+  std::vector<uint32_t> h_counts((size_t)g.chunk * kRowCounts);
   std::vector<double> h_sums((size_t)g.chunk * kRowSums);
-  for (uint32_t off = 0; off < n_locs; off += g.chunk) {
-    const uint32_t len = std::min(g.chunk, n_locs - off);
-    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
-    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    const ScanSegs sg = scan_segments(g, len);
-    ScanArgs a{};
-    a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.thn = c->d_ll_thn, a.lam = c->p.lam;
-    a.trait = trait ? c->d_scan_trait : nullptr, a.locs = d_locs;
-    a.npad = np, a.K = K, a.len = len, a.seg_len = sg.seg_len, a.ntiles = g.ntiles, a.part = c->d_scan_part;
-    scan_launch_chunk(a, sg.nseg, d_sums, d_counts, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(h_sums.data(), d_sums, (size_t)len * kRowSums * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h_counts.data(), d_counts, (size_t)len * kRowCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < len; ++i) {  // listed order
-      const double *s = &h_sums[(size_t)i * kRowSums];
-      const uint32_t *n = &h_counts[(size_t)i * kRowCounts];
-      if (fit_sums) std::copy(s, s + kScanFitSums, fit_sums + (size_t)(off + i) * kScanFitSums);
-      if (fit_counts) std::copy(n, n + kScanFitCounts, fit_counts + (size_t)(off + i) * kScanFitCounts);
-      if (trait_sums) std::copy(s + kScanFitSums, s + kRowSums, trait_sums + (size_t)(off + i) * kScanTraitSums);
-      if (trait_counts) trait_counts[off + i] = n[kScanFitCounts];
-    }
-  }
-  return TSAMD_OK;
+  return for_each_chunk(
+      c, locs, n_locs, g.chunk, d_locs, {{h_sums.data(), d_sums, kRowSums * sizeof(double)}, {h_counts.data(), d_counts, kRowCounts * sizeof(uint32_t)}},
+      [&](uint32_t len) {
+        const ScanSegs sg = scan_segments(g, len);
+        a.len = len, a.seg_len = sg.seg_len;
+        scan_launch_chunk(a, sg.nseg, d_sums, d_counts, c->stream);
+      },
+      [&](uint32_t off, uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i) {
+          const double *s = &h_sums[(size_t)i * kRowSums];
+          const uint32_t *n = &h_counts[(size_t)i * kRowCounts];
+          if (fit_sums) std::copy(s, s + kScanFitSums, fit_sums + (size_t)(off + i) * kScanFitSums);
+          if (fit_counts) std::copy(n, n + kScanFitCounts, fit_counts + (size_t)(off + i) * kScanFitCounts);
+          if (trait_sums) std::copy(s + kScanFitSums, s + kRowSums, trait_sums + (size_t)(off + i) * kScanTraitSums);
+          if (trait_counts) trait_counts[off + i] = n[kScanFitCounts];
+        }
+      });
 }
 
 // no context, no device work: z and p from the sums the caller has added across ranks (scan_statistics_row, csrc/tsamd_scan_plan.h)
@@ -2463,18 +2416,6 @@ static int state_copy(tsamd_ctx *c, void *host, void *dev, uint64_t bytes, bool 
   return TSAMD_OK;
 }
 
-// the device staging buffer of the individual part: allocated by the first export or import and kept (a hipFree per
-// call would synchronise the whole device, which other shards may share); tsamd_destroy frees it
-static int ensure_state_stage(tsamd_ctx *c, size_t bytes) {
-  if (c->state_bytes >= bytes) return TSAMD_OK;
-  hipFree(c->d_state);
-  c->d_state = nullptr;
-  c->state_bytes = 0;
-  HIP_TRY(c, hipMalloc((void **)&c->d_state, bytes));
-  c->state_bytes = bytes;
-  return TSAMD_OK;
-}
-
 // the slot of Ctl::st the next kernel of the sequence reads (it was written by the last one: parity (q - 1) & 1; a fresh
 // context's first kernel has parity 0 and reads slot 1, zeroed by tsamd_create)
 static uint32_t state_live_slot(const tsamd_ctx *c) { return (uint32_t)(c->q & 1u) ^ 1u; }
@@ -2501,8 +2442,8 @@ int tsamd_state_export(tsamd_ctx *c, void *indiv, uint64_t indiv_bytes, void *lo
   const uint32_t K = c->cfg.k;
   if (indiv) {
     uint8_t *pay = (uint8_t *)indiv + sizeof(tsamd_state_header);
-    if (int rc = ensure_state_stage(c, ip)) return rc;
-    double *d_stage = c->d_state;
+    HIP_TRY(c, c->d_state.reserve(ip));
+    double *d_stage = c->d_state.as<double>();
     const uint32_t TN = state_tile(K);
     hipError_t e = hipMemsetAsync((uint8_t *)d_stage + ip - 8, 0, 8, c->stream);  // (the zero padding behind an odd number of c_n)
     if (e == hipSuccess) {
@@ -2608,9 +2549,9 @@ int tsamd_state_import(tsamd_ctx *c, const void *indiv, uint64_t indiv_bytes, co
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (indiv) {
-    if (int rc = ensure_state_stage(c, ip)) return rc;
+    HIP_TRY(c, c->d_state.reserve(ip));
     const uint32_t TN = state_tile(K);
-    double *d_stage = c->d_state;
+    double *d_stage = c->d_state.as<double>();
     int rc = state_copy(c, (void *)((const uint8_t *)indiv + sizeof(tsamd_state_header)), d_stage, ip, false);
     hipError_t e = hipSuccess;
     if (rc == TSAMD_OK) {

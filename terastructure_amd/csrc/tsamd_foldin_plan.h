@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "tsamd_sweep_plan.h"
+
 #if defined(__HIPCC__)
 #define TSAMD_FI_HD __host__ __device__
 #else
@@ -95,10 +97,7 @@ TSAMD_FI_HD inline FoldinGeom foldin_geometry(uint32_t npad, uint32_t K, uint32_
   g.tile_n = kFoldinBlock * g.ipt;
   g.ntiles = (npad + g.tile_n - 1u) / g.tile_n;
   g.batch = K > kFoldinSpecializedK ? kFoldinWideBatch : kFoldinBatch;
-  if (cus < 1u) cus = 1u;
-  if (cus > 1024u) cus = 1024u;
-  uint64_t nseg = g.ntiles >= cus ? 1u : (2ull * cus + g.ntiles - 1u) / g.ntiles;
-  if (nseg > kFoldinMaxSegments) nseg = kFoldinMaxSegments;
+  uint64_t nseg = sweep_fill_segments(g.ntiles, cus, kFoldinMaxSegments);
   if (test_segments > 0u) nseg = test_segments < kFoldinMaxSegments ? test_segments : kFoldinMaxSegments;
   // the partials [nseg][K][npad] stay under the bound
   const uint64_t one = (uint64_t)npad * K * sizeof(double);

@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "tsamd_sweep_plan.h"
+
 #if defined(__HIPCC__)
 #define TSAMD_LL_HD __host__ __device__
 #else
@@ -56,10 +58,7 @@ TSAMD_LL_HD inline LoglikGeom loglik_geometry(uint32_t npad, uint32_t K, uint32_
   g.ipt = loglik_ipt(K);
   g.tile_n = kLoglikBlock * g.ipt;
   g.ntiles = (npad + g.tile_n - 1u) / g.tile_n;
-  if (cus < 1u) cus = 1u;
-  if (cus > 1024u) cus = 1024u;
-  uint64_t nseg = g.ntiles >= cus ? 1u : (2ull * cus + g.ntiles - 1u) / g.ntiles;
-  if (nseg > kLoglikMaxSegments) nseg = kLoglikMaxSegments;
+  uint64_t nseg = sweep_fill_segments(g.ntiles, cus, kLoglikMaxSegments);
   // the per-individual partials ([nseg][npad]) take at most half of the bound ...
   const uint64_t row = (uint64_t)npad * kLoglikPartBytes;
   const uint64_t fit = (kLoglikScratchBound / 2u) / row;
@@ -76,19 +75,9 @@ TSAMD_LL_HD inline LoglikGeom loglik_geometry(uint32_t npad, uint32_t K, uint32_
   return g;
 }
 
-// segments of a chunk of len locations: at least 8 locations each, so that a workgroup's theta load is shared
-struct LoglikSegs {
-  uint32_t nseg, seg_len;
-};
-TSAMD_LL_HD inline LoglikSegs loglik_segments(const LoglikGeom &g, uint32_t len) {
-  uint32_t nseg = (len + 7u) / 8u;
-  if (nseg > g.nseg_max) nseg = g.nseg_max;
-  if (nseg < 1u) nseg = 1u;
-  LoglikSegs s;
-  s.seg_len = (len + nseg - 1u) / nseg;
-  s.nseg = s.seg_len ? (len + s.seg_len - 1u) / s.seg_len : 1u;
-  return s;
-}
+// segments of a chunk of len locations (sweep_segments, tsamd_sweep_plan.h)
+using LoglikSegs = SweepSegs;
+TSAMD_LL_HD inline LoglikSegs loglik_segments(const LoglikGeom &g, uint32_t len) { return sweep_segments(g.nseg_max, len); }
 
 // bytes of the partial-sum buffers of a geometry
 TSAMD_LL_HD inline uint64_t loglik_scratch_bytes(const LoglikGeom &g, uint32_t npad) {

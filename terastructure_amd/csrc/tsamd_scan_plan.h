@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "tsamd_sweep_plan.h"
+
 #if defined(__HIPCC__)
 #define TSAMD_SC_HD __host__ __device__
 #else
@@ -126,11 +128,7 @@ TSAMD_SC_HD inline ScanGeom scan_geometry(uint32_t npad, uint32_t K, bool trait,
   g.tile_n = kScanBlock * g.ipt;
   g.ntiles = (npad + g.tile_n - 1u) / g.tile_n;
   g.values = scan_values(trait);
-  if (cus < 1u) cus = 1u;
-  if (cus > 1024u) cus = 1024u;
-  uint64_t nseg = g.ntiles >= cus ? 1u : (2ull * cus + g.ntiles - 1u) / g.ntiles;
-  if (nseg > kScanMaxSegments) nseg = kScanMaxSegments;
-  g.nseg_max = (uint32_t)nseg;
+  g.nseg_max = (uint32_t)sweep_fill_segments(g.ntiles, cus, kScanMaxSegments);
   uint64_t chunk = kScanScratchBound / ((uint64_t)g.ntiles * g.values * sizeof(double));
   if (chunk > kScanMaxChunk) chunk = kScanMaxChunk;
   if (test_chunk > 0u && chunk > test_chunk) chunk = test_chunk;
@@ -139,19 +137,9 @@ TSAMD_SC_HD inline ScanGeom scan_geometry(uint32_t npad, uint32_t K, bool trait,
   return g;
 }
 
-// segments of a chunk of len locations: at least 8 locations each, so that a workgroup's theta load is shared
-struct ScanSegs {
-  uint32_t nseg, seg_len;
-};
-TSAMD_SC_HD inline ScanSegs scan_segments(const ScanGeom &g, uint32_t len) {
-  uint32_t nseg = (len + 7u) / 8u;
-  if (nseg > g.nseg_max) nseg = g.nseg_max;
-  if (nseg < 1u) nseg = 1u;
-  ScanSegs s;
-  s.seg_len = (len + nseg - 1u) / nseg;
-  s.nseg = s.seg_len ? (len + s.seg_len - 1u) / s.seg_len : 1u;
-  return s;
-}
+// segments of a chunk of len locations (sweep_segments, tsamd_sweep_plan.h)
+using ScanSegs = SweepSegs;
+TSAMD_SC_HD inline ScanSegs scan_segments(const ScanGeom &g, uint32_t len) { return sweep_segments(g.nseg_max, len); }
 
 // bytes of the partial-sum buffer of a geometry
 TSAMD_SC_HD inline uint64_t scan_scratch_bytes(const ScanGeom &g) {

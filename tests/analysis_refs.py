@@ -314,13 +314,13 @@ def pick_lists(c, seed, begin=0, count=None):
     assert c.ids.size == KIN_M
 
 
-def plant_every_k(k):
-    """PSD genotypes with 10 % missing, the initial gamma, a "trained" lambda = 1 + c (beta, 1 - beta) with a per-location
+def plant_every_k(k, n=None, l=EVERY_K_L):
+    """(n, l: every_k_n(k) and EVERY_K_L unless given)  PSD genotypes with 10 % missing, the initial gamma, a "trained" lambda = 1 + c (beta, 1 - beta) with a per-location
     c in (0, 200), and held-out lists at locations 0, l / 2 and l - 1 that include individuals 0 and n - 1"""
     from helpers import init_gamma, psd_genotypes
 
     c = Case()
-    n, l = every_k_n(k), EVERY_K_L
+    n = every_k_n(k) if n is None else n
     c.n, c.l, c.k = n, l, k
     c.y, _, beta = psd_genotypes(n, l, k, 7000 + k, missing_rate=0.1)
     rng = np.random.default_rng(7200 + k)
