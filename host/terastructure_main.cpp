@@ -155,6 +155,11 @@ struct Options {
   double kinship_min = 0.044194173824159216;  // -kinship-min: pairs below are not listed (2^-4.5: third-degree relatives and closer)
   bool scan = false;            // extension: per-SNP fit and association tests of the final model (scan.txt)
   std::string pheno;            // -scan: one trait value per individual from this file
+  uint32_t ld = 0;              // extension: -ld <window>: structure-adjusted LD of nearby locations under the final model, and pruning
+  bool ld_set = false, ld_rows_set = false;
+  double ld_r2 = 0.2;           // -ld-r2: pruning drops a location whose r^2 with a kept one inside the window exceeds this
+  double ld_min = 0.05;         // -ld-min: pairs with a smaller r^2 are not listed in ld.txt
+  uint32_t ld_rows = 0;         // -ld-rows: rows of the band the host holds at a time (0: as many as 256 MB hold)
 };
 
 struct Timing {
@@ -168,6 +173,9 @@ struct Timing {
   double kinship = 0;  // -kinship: tsamd_kinship over all locations and writing its files
   uint32_t kinship_pairs = 0;
   double scan = 0;  // -scan: tsamd_snp_scan over all locations and writing scan.txt
+  double ld = 0;    // -ld: tsamd_ld over all locations and writing its files
+  uint64_t ld_pairs = 0;
+  uint32_t ld_kept = 0;
   uint32_t logls = 0;
 };
 
@@ -367,7 +375,16 @@ void usage() {
           "\t\t\t z_het, p_het (heterozygote count against the model), z_freq, p_freq (allele count against it)\n"
           "\t-pheno <file>\t -scan: one trait value per line (theta.txt's order, exactly -n lines; NA or nan = not\n"
           "\t\t\t phenotyped); scan.txt gains n_t, z_trait, p_trait: the score test of the trait against the\n"
-          "\t\t\t genotype residual y - 2q\n");
+          "\t\t\t genotype residual y - 2q\n"
+          "\t-ld <window>\t with the final model (a plain run, -resume or -project): LD of every pair of locations at most\n"
+          "\t\t\t <window> (1 to 1024) positions apart, adjusted for structure: the correlation r of the genotype\n"
+          "\t\t\t residuals (y - 2q) / sqrt(2q (1 - q)).  Writes ld.txt (i, j, r, r2, n, p; pairs at or above -ld-min)\n"
+          "\t\t\t and an LD pruning, prune.in / prune.out: 0-based location indices in -locations-file's format\n"
+          "\t-ld-r2 <max>\t -ld: in ascending order a location is pruned when its r2 with a kept location inside the\n"
+          "\t\t\t window exceeds this (default 0.2)\n"
+          "\t-ld-min <r2>\t -ld: lowest r2 listed in ld.txt (default 0.05; 0 lists every pair of the band)\n"
+          "\t-ld-rows <rows>\t -ld: locations whose rows of the band the host holds at a time (default: as many as 256 MB\n"
+          "\t\t\t of host memory hold, at least 4096); the files do not depend on it beyond the rounding of r\n");
   fflush(stdout);
 }
 
@@ -844,12 +861,15 @@ void write_timing(Run &r) {
   if (!r.o.kinship.empty())
     fprintf(f, "kinship (-kinship): %.3f (%zu individuals, %u pairs listed)\n", t.kinship, r.kin_ids.size(), t.kinship_pairs);
   if (r.o.scan) fprintf(f, "scan (-scan): %.3f (%u locations%s)\n", t.scan, r.o.l, r.o.pheno.empty() ? "" : ", with a trait");
+  if (r.o.ld_set)
+    fprintf(f, "ld (-ld): %.3f (window %u, %llu pairs listed, %u of %u locations kept)\n", t.ld, r.o.ld, (unsigned long long)t.ld_pairs, t.ld_kept, r.o.l);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
 
 void kinship(Run &r);  // (-kinship, below)
 void scan(Run &r);     // (-scan, below)
+void ld(Run &r);       // (-ld, below)
 
 // -project: the checkpoint's lambda into every context in chunks, tsamd_fold_in over all locations from gamma = 1 (no
 // validation sample is drawn: every stored genotype counts), then theta.txt / gamma.txt through the usual writer and
@@ -891,6 +911,7 @@ void project(Run &r, const ckpt::Buf &loc) {
   r.tm.project = sw.lap();
   if (!o.kinship.empty()) kinship(r);  // (the folded-in theta against the file's lambda)
   if (o.scan) scan(r);                 // likewise
+  if (o.ld_set) ld(r);                 // likewise
   finish_saves(r);
   write_timing(r);
   printf("+ done: %u updates, %u of %u individuals converged\n", r.tm.project_iters_run, r.tm.project_converged, o.n);
@@ -1077,6 +1098,67 @@ void scan(Run &r) {
   fclose(f);
   r.tm.scan += sw.lap();
   r.lerr("scan of %u locations%s", l, trait ? " with a trait" : "");
+}
+
+// -ld: tsamd_ld over all l locations under the state of the final save_model.  The locations go in blocks of rows (-ld-rows)
+// with an overlap of the window -- by default what the host holds of a block's band, 40 bytes per entry of [rows + window]
+// [window + 1] (the sum of num and cnt over the shards, one shard's, r and p), stays under 256 MB, or is 4096 rows -- and the shards'
+// bands are added in shard order; r and p from tsamd_ld_statistics.  ld.txt, one line per pair i < j <= i + window with
+// r^2 >= -ld-min: "i \t j \t r \t r2 \t n \t p".  The pruning is tsamd_ld_prune's rule carried across the blocks: rows in
+// ascending order, a row that is still kept drops the later locations whose r^2 with it exceeds -ld-r2.  prune.in / prune.out:
+// one 0-based location per line.
+void ld(Run &r) {
+  Stopwatch sw;
+  const Options &o = r.o;
+  const uint32_t l = o.l, w = o.ld, w1 = w + 1u;
+  const uint64_t entry = 4u * sizeof(double) + 2u * sizeof(uint32_t), fit = (256ull << 20) / ((uint64_t)w1 * entry);
+  const uint32_t rows_max =  // (by default whole internal chunks of the library)
+      (uint32_t)std::min<uint64_t>(l, o.ld_rows ? o.ld_rows : std::max<uint64_t>(4096u, fit / 4096u * 4096u));
+  FILE *f = fopen(r.file_str("/ld.txt").c_str(), "w"), *fin = fopen(r.file_str("/prune.in").c_str(), "w"), *fout = fopen(r.file_str("/prune.out").c_str(), "w");
+  if (!f || !fin || !fout) {
+    r.lerr("cannot open ld.txt / prune.in / prune.out:%s\n", strerror(errno));
+    exit(-1);
+  }
+  std::vector<uint8_t> dropped(l, 0);
+  std::vector<uint32_t> locs;
+  std::vector<double> num, n1, rr, pp;
+  std::vector<uint32_t> cnt, c1;
+  for (uint32_t b0 = 0; b0 < l; b0 += rows_max) {
+    const uint32_t rows = std::min(rows_max, l - b0), n_locs = rows + std::min(w, l - b0 - rows);  // the block's rows and their overlap
+    const size_t count = (size_t)n_locs * w1;
+    locs.resize(n_locs);
+    for (uint32_t i = 0; i < n_locs; ++i) locs[i] = b0 + i;
+    num.assign(count, 0.0), cnt.assign(count, 0u), n1.resize(count), c1.resize(count), rr.resize(count), pp.resize(count);
+    for (size_t i = 0; i < r.ctxs.size(); ++i) {  // shard after shard; no exchange is involved
+      r.ctx = r.ctxs[i];
+      TS(r, tsamd_ld(r.ctxs[i], locs.data(), n_locs, w, n1.data(), c1.data()));
+      for (size_t x = 0; x < count; ++x) num[x] += n1[x], cnt[x] += c1[x];
+    }
+    r.ctx = r.ctxs[0];
+    if (tsamd_ld_statistics(num.data(), cnt.data(), n_locs, w, rr.data(), pp.data()) != 0) {
+      r.lerr("tsamd_ld_statistics: %s\n", tsamd_last_error(nullptr));
+      exit(-1);
+    }
+    for (uint32_t i = 0; i < rows; ++i) {  // (the overlap's rows belong to the next block: their windows are cut short here)
+      const uint32_t gi = b0 + i;
+      for (uint32_t d = 1; d <= w && gi + d < l; ++d) {
+        const size_t x = (size_t)i * w1 + d;
+        const double r2 = rr[x] * rr[x];
+        if (!dropped[gi] && r2 > o.ld_r2) dropped[gi + d] = 1;
+        if (!(r2 >= o.ld_min)) continue;
+        fprintf(f, "%u\t%u\t%.8f\t%.8f\t%u\t%.6e\n", gi, gi + d, rr[x], r2, cnt[x], pp[x]);
+        r.tm.ld_pairs++;
+      }
+      fprintf(dropped[gi] ? fout : fin, "%u\n", gi);
+      r.tm.ld_kept += dropped[gi] ? 0u : 1u;
+    }
+  }
+  fclose(f);
+  fclose(fin);
+  fclose(fout);
+  r.tm.ld += sw.lap();
+  r.lerr("ld of %u locations, window %u: %llu pairs at or above r2 %g, %u locations kept at r2 <= %g", l, w, (unsigned long long)r.tm.ld_pairs, o.ld_min,
+         r.tm.ld_kept, o.ld_r2);
 }
 
 // compute_likelihood(first, validation = true) (src/snpsamplinge.cc:461-544);
@@ -1413,6 +1495,16 @@ int main(int argc, char **argv) {
       o.scan = true;
     } else if (!strcmp(a, "-pheno")) {
       o.pheno = need(a);
+    } else if (!strcmp(a, "-ld")) {
+      o.ld = (uint32_t)std::max(0, atoi(need(a)));
+      o.ld_set = true;
+    } else if (!strcmp(a, "-ld-r2")) {
+      o.ld_r2 = atof(need(a));
+    } else if (!strcmp(a, "-ld-min")) {
+      o.ld_min = atof(need(a));
+    } else if (!strcmp(a, "-ld-rows")) {
+      o.ld_rows = (uint32_t)std::max(0, atoi(need(a)));
+      o.ld_rows_set = true;
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -1493,6 +1585,22 @@ int main(int argc, char **argv) {
     std::string why;
     if (!o.pheno.empty() && !read_pheno(r, &why)) {
       fprintf(stderr, "error: -pheno: %s\n", why.c_str());
+      return -1;
+    }
+  }
+
+  // -ld: the window and the thresholds are checked before anything else exists
+  if (o.ld_set) {
+    if (o.compute_beta || o.ingest_only) {
+      fprintf(stderr, "error: -ld evaluates a run's final model; it does not go with %s\n", o.compute_beta ? "-compute-beta" : "-ingest-only");
+      return -1;
+    }
+    if (o.ld == 0 || o.ld > TSAMD_LD_MAX_WINDOW || !(o.ld_r2 >= 0.0) || !std::isfinite(o.ld_r2) || !std::isfinite(o.ld_min)) {
+      fprintf(stderr, "error: -ld needs a window of 1 to %d locations, -ld-r2 finite and not negative, -ld-min finite\n", TSAMD_LD_MAX_WINDOW);
+      return -1;
+    }
+    if (o.ld_rows_set && o.ld_rows == 0) {
+      fprintf(stderr, "error: -ld-rows needs at least 1 location\n");
       return -1;
     }
   }
@@ -1693,6 +1801,7 @@ int main(int argc, char **argv) {
   if (o.logl) train_likelihood(r, true);  // the state of the final save_model: the per-location and per-individual files
   if (!o.kinship.empty()) kinship(r);     // likewise
   if (o.scan) scan(r);                    // likewise
+  if (o.ld_set) ld(r);                    // likewise
   finish_saves(r);  // gamma.txt / theta.txt complete and closed before the process ends
   write_timing(r);
   destroy_all(r);

@@ -71,9 +71,11 @@ typedef struct tsamd_config {
                                         (locations per internal chunk of tsamd_train_loglik), TSAMD_TEST_FOLDIN_SEGMENTS (tsamd_fold_in:
                                         cut the list into at most that many segments, whatever the device's size), TSAMD_TEST_KIN_CHUNK
                                         (locations per internal chunk of tsamd_kinship), TSAMD_TEST_KIN_SEGMENTS (tsamd_kinship: cut a
-                                        chunk into at most that many segments, whatever the device's size) and TSAMD_TEST_SCAN_CHUNK
+                                        chunk into at most that many segments, whatever the device's size), TSAMD_TEST_SCAN_CHUNK
                                         (locations per internal chunk of tsamd_snp_scan, whose segment count TSAMD_TEST_MAX_WORKGROUPS
-                                        sets as for the other sweeps) */
+                                        sets as for the other sweeps), TSAMD_TEST_LD_CHUNK (locations per internal chunk of tsamd_ld,
+                                        rounded up to whole tiles of 64) and TSAMD_TEST_LD_BLOCK (individuals per internal block of
+                                        tsamd_ld, whose segment count TSAMD_TEST_MAX_WORKGROUPS sets as for the other sweeps) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -291,6 +293,39 @@ int tsamd_snp_scan(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs,
 int tsamd_scan_statistics(const double *fit_sums, const uint32_t *fit_counts,
                           const double *trait_sums /* may be NULL */, const uint32_t *trait_counts /* may be NULL */,
                           uint32_t n_locs, double *stats /* [n_locs][6] */);
+
+/* Structure-adjusted linkage disequilibrium of nearby listed locations: the LD of the genotype residuals given the
+ * individual-specific allele frequencies (r_S of Mangin et al. 2012) on the model the context holds; changes no state (gamma, w,
+ * lambda, c_n, counters, the pending step and held-out folds stay as they are).  With q = sum_k Ebeta[j][k] * Etheta[n][k] (the
+ * values tsamd_get_ebeta and tsamd_get_theta return at that moment: a pending gamma step stays pending), h = 2q(1-q) and y the
+ * stored genotype,
+ *   z(n,j) = (y - 2q) / sqrt(h),  stored where the code is not 01 (missing, held out by tsamd_set_heldout, padding) and h > 0,
+ * so that E z = 0 and Var z = 1 under the model.  The outputs are BANDS: for list positions i = 0 .. n_locs-1, row i has
+ * window + 1 columns d = 0 .. window, column d the pair (i, i + d), column 0 the location with itself; every column with
+ * i + d >= n_locs is 0:
+ *   num[i][d] = sum_n z(n, loc_i) z(n, loc_{i+d})  over the shard's individuals stored at both locations,
+ *   cnt[i][d] = the number of those individuals.
+ * locs == NULL means locations 0 .. n_locs-1 (n_locs <= l); the order of the list defines who neighbours whom; a repeated
+ * location is a row of its own.  Each output may be NULL, not both.  z is computed once per entry and internal chunk; the two
+ * products run on the matrix cores (v_mfma_f64_16x16x4_f64, csrc/tsamd_ld_kernels.h), the count as the product of the 0 / 1
+ * masks.  No floating-point atomics, a fixed summation order: two identical calls give identical bits; cnt is exact; a pair's
+ * num may depend on how the library cuts the list into chunks and the shard into blocks and segments -- by rounding only.
+ * Synchronous; settles the context first like every getter.  TSAMD_EINVAL for n_locs == 0, window == 0 or above
+ * TSAMD_LD_MAX_WINDOW, a location >= l, or both outputs NULL; every k the context accepts is served.  On a sharded context every
+ * rank answers for its own shard; both outputs are plain sums, so the caller adds the ranks' bands: no exchange is involved. */
+#define TSAMD_LD_MAX_WINDOW 1024
+int tsamd_ld(tsamd_ctx *ctx, const uint32_t *locs, uint32_t n_locs, uint32_t window,
+             double *num /* [n_locs][window+1], may be NULL */, uint32_t *cnt /* [n_locs][window+1], may be NULL */);
+/* r and p of every entry of a band of tsamd_ld, added across ranks by the caller.  Takes no context and does no device work: it
+ * runs without a GPU.  r = num / cnt, 0 where cnt < 2; p = erfc(|r| sqrt(cnt) / sqrt(2)): under the model r sqrt(cnt) of an
+ * unlinked pair is a standard normal.  TSAMD_EINVAL for n_locs == 0 or a NULL num, cnt or r (the message:
+ * tsamd_last_error(NULL)). */
+int tsamd_ld_statistics(const double *num, const uint32_t *cnt, uint32_t n_locs, uint32_t window,
+                        double *r /* [n_locs][window+1] */, double *p /* [n_locs][window+1], may be NULL */);
+/* LD pruning on a band of r: the positions go in ascending order, and position i is dropped (keep[i] = 0) if and only if some
+ * KEPT position j in [i - window, i) has r[j][i - j]^2 > r2_max; otherwise keep[i] = 1.  No context, no device work.
+ * TSAMD_EINVAL for n_locs == 0, a NULL r or keep, or an r2_max that is negative or not finite. */
+int tsamd_ld_prune(const double *r, uint32_t n_locs, uint32_t window, double r2_max, uint8_t *keep /* [n_locs] */);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

@@ -16,6 +16,7 @@ LAUNCH_PER_PASS, LAUNCH_PER_SNP, LAUNCH_PER_SCHEDULE = 0, 1, 2  # tsamd_set_laun
 PASS_HIST_BINS = 128
 KIN_MAX_M = 32768  # TSAMD_KIN_MAX_M
 SCAN_FIT_SUMS, SCAN_FIT_COUNTS, SCAN_TRAIT_SUMS, SCAN_STATS = 4, 3, 6, 6  # TSAMD_SCAN_*
+LD_MAX_WINDOW = 1024  # TSAMD_LD_MAX_WINDOW
 
 
 class Config(C.Structure):
@@ -77,6 +78,9 @@ SYMBOLS = {
     "tsamd_kinship": (_int, [_vp, _pu32, _u32, _pu32, _u32, _pd, _pd, _pd]),
     "tsamd_snp_scan": (_int, [_vp, _pu32, _u32, _pd, _pd, _pu32, _pd, _pu32]),
     "tsamd_scan_statistics": (_int, [_pd, _pu32, _pd, _pu32, _u32, _pd]),
+    "tsamd_ld": (_int, [_vp, _pu32, _u32, _u32, _pd, _pu32]),
+    "tsamd_ld_statistics": (_int, [_pd, _pu32, _u32, _u32, _pd, _pd]),
+    "tsamd_ld_prune": (_int, [_pd, _u32, _u32, _dbl, _pu8]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

@@ -79,6 +79,8 @@ def _units():
     units.append((os.path.join(OBJ_DIR, "kin.o"), os.path.join(CSRC, "tsamd_kin.hip"), []))
     # tsamd_snp_scan's kernels, likewise (csrc/tsamd_scan.hip)
     units.append((os.path.join(OBJ_DIR, "scan.o"), os.path.join(CSRC, "tsamd_scan.hip"), []))
+    # tsamd_ld's kernels, likewise (csrc/tsamd_ld.hip)
+    units.append((os.path.join(OBJ_DIR, "ld.o"), os.path.join(CSRC, "tsamd_ld.hip"), []))
     return units
 
 

@@ -28,6 +28,7 @@
 #include "tsamd_loglik_plan.h"
 #include "tsamd_foldin_plan.h"
 #include "tsamd_kin_plan.h"
+#include "tsamd_ld_plan.h"
 #include "tsamd_scan_plan.h"
 #include "tsamd_unit.h"
 
@@ -152,6 +153,10 @@ struct tsamd_ctx {
   // tsamd_snp_scan: the tiles' partials (scan_geometry: at most kScanScratchBound bytes), the chunk's rows and locations ([cap][10] sums,
   // [cap][4] counts, [cap] locations: cap = the bytes / kScanChunkRow), the trait padded to npad; allocated on first use
   DevBuf d_scan_part, d_scan_chunk, d_scan_trait;
+  // tsamd_ld: Z and M of a block of individuals, the segments' partial tiles, a chunk's accumulators (ld_geometry: at most
+  // kLdScratchBound bytes each), the chunk's rows of the band ([chunk][window + 1] num, then cnt) and its locations with their
+  // overlap; allocated on first use
+  DevBuf d_ld_zm, d_ld_part, d_ld_acc, d_ld_band, d_ld_locs;
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -562,7 +567,7 @@ int check_locs(tsamd_ctx *c, uint32_t first_loc, uint32_t n_locs) {
   return TSAMD_OK;
 }
 
-// ---- the front end of the analysis calls: tsamd_train_loglik, tsamd_fold_in, tsamd_kinship, tsamd_snp_scan ---------------------
+// ---- the front end of the analysis calls: tsamd_train_loglik, tsamd_fold_in, tsamd_kinship, tsamd_snp_scan, tsamd_ld ---------------------
 
 // the list of locations such a call takes (locs == NULL: locations 0 .. n_locs - 1)
 int check_loc_list(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs) {
@@ -592,24 +597,25 @@ int runtime_k_theta(tsamd_ctx *c, const double **thn) {
   return TSAMD_OK;
 }
 
-// The chunk loop of train_loglik, kinship and snp_scan.  The listed locations go chunk after chunk: a chunk's locations are
-// staged and uploaded to d_locs, enqueue(len) launches its kernels, its results -- row_bytes per listed location from dev to
-// host, for each of outs -- are fetched, the stream is waited for (the staging vector and the hosts' buffers are reused) and
-// collect(off, len) takes the results, so in listed order.
+// The chunk loop of train_loglik, kinship, snp_scan and ld.  The listed locations go chunk after chunk: a chunk's locations --
+// and up to `halo` of those that follow them (ld's overlap; 0 for the others) -- are staged and uploaded to d_locs,
+// enqueue(off, len) launches its kernels, its results -- row_bytes per listed location from dev to host, for each of outs --
+// are fetched, the stream is waited for (the staging vector and the hosts' buffers are reused) and collect(off, len) takes the
+// results, so in listed order.
 struct ChunkOut {
   void *host;
   const void *dev;
   size_t row_bytes;
 };
 template <class Enqueue, class Collect>
-int for_each_chunk(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t chunk, uint32_t *d_locs, std::initializer_list<ChunkOut> outs,
-                   Enqueue enqueue, Collect collect) {
-  std::vector<uint32_t> h_locs(chunk);
+int for_each_chunk(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t chunk, uint32_t halo, uint32_t *d_locs,
+                   std::initializer_list<ChunkOut> outs, Enqueue enqueue, Collect collect) {
+  std::vector<uint32_t> h_locs((size_t)chunk + halo);
   for (uint32_t off = 0; off < n_locs; off += chunk) {
-    const uint32_t len = std::min(chunk, n_locs - off);
-    for (uint32_t i = 0; i < len; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
-    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)len * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    enqueue(len);
+    const uint32_t len = std::min(chunk, n_locs - off), staged = len + std::min(halo, n_locs - off - len);
+    for (uint32_t i = 0; i < staged; ++i) h_locs[i] = locs ? locs[off + i] : off + i;
+    HIP_TRY(c, hipMemcpyAsync(d_locs, h_locs.data(), (size_t)staged * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    enqueue(off, len);
     HIP_TRY(c, hipGetLastError());
     for (const ChunkOut &o : outs) HIP_TRY(c, hipMemcpyAsync(o.host, o.dev, (size_t)len * o.row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -688,7 +694,8 @@ void tsamd_destroy(tsamd_ctx *c) {
   if (c->h_occupy) hipHostFree(c->h_occupy);
   for (DevBuf *b : {&c->d_hids, &c->d_hy, &c->d_hterms, &c->d_hreq, &c->d_fold_ids, &c->d_fold_orig, &c->d_hsums, &c->d_ll_part, &c->d_ll_chunk,
                     &c->d_ll_acc, &c->d_ll_thn, &c->d_fi_part, &c->d_fi_ind, &c->d_fi_locs, &c->d_kin_rs, &c->d_kin_part, &c->d_kin_acc,
-                    &c->d_kin_idx, &c->d_scan_part, &c->d_scan_chunk, &c->d_scan_trait})
+                    &c->d_kin_idx, &c->d_scan_part, &c->d_scan_chunk, &c->d_scan_trait, &c->d_ld_zm, &c->d_ld_part,
+                    &c->d_ld_acc, &c->d_ld_band, &c->d_ld_locs})
     b->free();
   if (c->h_stage) hipHostFree(c->h_stage);
   c->d_state.free();
@@ -1751,8 +1758,8 @@ int tsamd_train_loglik(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, doub
   double total = 0.0;
   uint64_t total_cnt = 0;
   const int rc = for_each_chunk(
-      c, locs, n_locs, chunk, d_locs, {{h_sum.data(), d_sum, sizeof(double)}, {h_cnt.data(), d_cnt, sizeof(uint32_t)}},
-      [&](uint32_t len) {
+      c, locs, n_locs, chunk, 0u, d_locs, {{h_sum.data(), d_sum, sizeof(double)}, {h_cnt.data(), d_cnt, sizeof(uint32_t)}},
+      [&](uint32_t, uint32_t len) {
         const LoglikSegs sg = loglik_segments(g, len);
         a.len = len, a.seg_len = sg.seg_len;
         loglik_launch_chunk(a, sg.nseg, d_sum, d_cnt, acc_sum, acc_cnt, c->stream);
@@ -1875,8 +1882,8 @@ int tsamd_kinship(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32
   a.npad = c->npad, a.K = c->cfg.k, a.mpad = g.mpad, a.ntiles = g.ntiles;
   a.r = c->d_kin_rs.as<double>(), a.s = a.r + (size_t)chunk4 * g.mpad, a.part = c->d_kin_part.as<double>(), a.num = d_num, a.den = d_den;
   const int rc = for_each_chunk(
-      c, locs, n_locs, g.chunk, d_locs, {},
-      [&](uint32_t len) {
+      c, locs, n_locs, g.chunk, 0u, d_locs, {},
+      [&](uint32_t, uint32_t len) {
         a.len = len, a.len4 = kin_round_step(len);
         const KinSegs sg = kin_segments(g, len);
         kin_launch_resid(a, c->stream);
@@ -1948,8 +1955,8 @@ int tsamd_snp_scan(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, const do
   std::vector<uint32_t> h_counts((size_t)g.chunk * kRowCounts);
   std::vector<double> h_sums((size_t)g.chunk * kRowSums);
   return for_each_chunk(
-      c, locs, n_locs, g.chunk, d_locs, {{h_sums.data(), d_sums, kRowSums * sizeof(double)}, {h_counts.data(), d_counts, kRowCounts * sizeof(uint32_t)}},
-      [&](uint32_t len) {
+      c, locs, n_locs, g.chunk, 0u, d_locs, {{h_sums.data(), d_sums, kRowSums * sizeof(double)}, {h_counts.data(), d_counts, kRowCounts * sizeof(uint32_t)}},
+      [&](uint32_t, uint32_t len) {
         const ScanSegs sg = scan_segments(g, len);
         a.len = len, a.seg_len = sg.seg_len;
         scan_launch_chunk(a, sg.nseg, d_sums, d_counts, c->stream);
@@ -1975,6 +1982,76 @@ int tsamd_scan_statistics(const double *fit_sums, const uint32_t *fit_counts, co
   for (uint32_t i = 0; i < n_locs; ++i)
     scan_statistics_row(fit_sums + (size_t)i * kScanFitSums, fit_counts + (size_t)i * kScanFitCounts,
                         trait ? trait_sums + (size_t)i * kScanTraitSums : nullptr, trait ? trait_counts[i] : 0u, stats + (size_t)i * kScanStats);
+  return TSAMD_OK;
+}
+
+// Chunk after chunk of whole location tiles (for_each_chunk, the chunk's overlap staged with it): per chunk the shard's
+// individuals block after block -- Z and M of the block once (ts_ld_resid), the band's tile pairs on the matrix cores (ts_ld_syrk,
+// ts_ld_finish: csrc/tsamd_ld_kernels.h) -- then the chunk's rows of the band (ts_ld_band); reads the state only.
+int tsamd_ld(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs, uint32_t window, double *num, uint32_t *cnt) {
+  CHECK_CTX(c);
+  static_assert(TSAMD_LD_MAX_WINDOW == kLdMaxWindow, "the header's bound is the plan's");
+  if (n_locs == 0) return check_loc_list(c, locs, n_locs);
+  if (window == 0 || window > TSAMD_LD_MAX_WINDOW)
+    return fail(c, TSAMD_EINVAL, "window = %u must lie in 1 .. TSAMD_LD_MAX_WINDOW = %u", window, (uint32_t)TSAMD_LD_MAX_WINDOW);
+  if (!num && !cnt) return fail(c, TSAMD_EINVAL, "num and cnt are both NULL");
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const LdGeom g = ld_geometry(c->n_local, n_locs, window, device_width(c), test_hook(c, "TSAMD_TEST_LD_CHUNK"), test_hook(c, "TSAMD_TEST_LD_BLOCK"));
+  const uint32_t halo = g.ov * kLdTile, w1 = window + 1u;
+
+  HIP_TRY(c, c->d_ld_zm.reserve((size_t)ld_zm_bytes(g)));
+  HIP_TRY(c, c->d_ld_part.reserve((size_t)ld_part_bytes(g)));
+  HIP_TRY(c, c->d_ld_acc.reserve((size_t)ld_acc_bytes(g)));
+  HIP_TRY(c, c->d_ld_band.reserve((size_t)ld_band_bytes(g)));
+  HIP_TRY(c, c->d_ld_locs.reserve(((size_t)g.chunk + halo) * sizeof(uint32_t)));
+  double *d_num = c->d_ld_band.as<double>();  // (the doubles first: both arrays start on a multiple of 8 bytes)
+  uint32_t *d_cnt = (uint32_t *)(d_num + (size_t)g.chunk * w1), *d_locs = c->d_ld_locs.as<uint32_t>();
+
+  LdArgs a{};
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam, a.locs = d_locs;
+  a.npad = c->npad, a.n_local = c->n_local, a.K = c->cfg.k, a.lpad = g.lpad;
+  a.z = c->d_ld_zm.as<double>(), a.m = a.z + (size_t)g.block * g.lpad, a.part = c->d_ld_part.as<double>(), a.acc = c->d_ld_acc.as<double>();
+  std::vector<double> h_num(num ? (size_t)g.chunk * w1 : 0);
+  std::vector<uint32_t> h_cnt(cnt ? (size_t)g.chunk * w1 : 0);
+  std::initializer_list<ChunkOut> both = {{h_num.data(), d_num, w1 * sizeof(double)}, {h_cnt.data(), d_cnt, w1 * sizeof(uint32_t)}};
+  std::initializer_list<ChunkOut> only_num = {{h_num.data(), d_num, w1 * sizeof(double)}}, only_cnt = {{h_cnt.data(), d_cnt, w1 * sizeof(uint32_t)}};
+  return for_each_chunk(
+      c, locs, n_locs, g.chunk, halo, d_locs, num && cnt ? both : num ? only_num : only_cnt,
+      [&](uint32_t off, uint32_t) {
+        const LdChunk ch = ld_chunk(g, n_locs, off);
+        a.ncols = ch.len + ch.halo;
+        (void)hipMemsetAsync(a.acc, 0, (size_t)ch.npairs * kLdTileBytes, c->stream);  // (a failure surfaces at the chunk's hipGetLastError)
+        for (uint32_t i0 = 0; i0 < c->n_local; i0 += g.block) {
+          a.ind0 = i0, a.blen = std::min(g.block, c->n_local - i0), a.rows4 = ld_round_step(a.blen);
+          const LdSegs sg = ld_segments(g, a.blen);
+          ld_launch_resid(a, c->stream);
+          for (uint32_t p0 = 0; p0 < ch.npairs; p0 += g.pairs_per_launch)
+            ld_launch_pairs(a, ch, g.ov, p0, std::min(g.pairs_per_launch, ch.npairs - p0), sg, c->stream);
+        }
+        ld_launch_band(a, ch, g.ov, window, d_num, d_cnt, c->stream);
+      },
+      [&](uint32_t off, uint32_t len) {
+        if (num) std::copy(h_num.begin(), h_num.begin() + (size_t)len * w1, num + (size_t)off * w1);
+        if (cnt) std::copy(h_cnt.begin(), h_cnt.begin() + (size_t)len * w1, cnt + (size_t)off * w1);
+      });
+}
+
+// no context, no device work: r and p of every entry of a band the caller has added across ranks (ld_statistics, csrc/tsamd_ld_plan.h)
+int tsamd_ld_statistics(const double *num, const uint32_t *cnt, uint32_t n_locs, uint32_t window, double *r, double *p) {
+  if (n_locs == 0) return fail(nullptr, TSAMD_EINVAL, "n_locs must be positive");
+  if (!num || !cnt || !r) return fail(nullptr, TSAMD_EINVAL, "num, cnt and r must not be NULL");
+  ld_statistics(num, cnt, (uint64_t)n_locs * ((uint64_t)window + 1u), r, p);
+  return TSAMD_OK;
+}
+
+// likewise: the positions an LD pruning keeps (ld_prune, csrc/tsamd_ld_plan.h)
+int tsamd_ld_prune(const double *r, uint32_t n_locs, uint32_t window, double r2_max, uint8_t *keep) {
+  if (n_locs == 0) return fail(nullptr, TSAMD_EINVAL, "n_locs must be positive");
+  if (!r || !keep) return fail(nullptr, TSAMD_EINVAL, "r and keep must not be NULL");
+  if (!(r2_max >= 0.0) || !std::isfinite(r2_max)) return fail(nullptr, TSAMD_EINVAL, "r2_max must be finite and not negative");
+  ld_prune(r, n_locs, window, r2_max, keep);
   return TSAMD_OK;
 }
 

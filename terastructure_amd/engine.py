@@ -63,6 +63,35 @@ def scan_statistics(fit_sums, fit_counts, trait_sums=None, trait_counts=None):
     return out
 
 
+def ld_statistics(num, cnt):
+    """(r, p), both [n_locs][window + 1], from the bands of Engine.ld (added across shards by the caller): r = num / cnt (0 where
+    cnt < 2), p = erfc(|r| sqrt(cnt) / sqrt(2)) -- tsamd_ld_statistics.  No device work: runs without a GPU."""
+    h = _lib.load()
+    nu = np.ascontiguousarray(num, dtype=np.float64)
+    cn = np.ascontiguousarray(cnt, dtype=np.uint32)
+    if nu.ndim != 2 or nu.shape != cn.shape or nu.shape[1] < 1:
+        raise ValueError("num and cnt must be bands of one shape [n_locs][window + 1]")
+    r, p = np.zeros(nu.shape, dtype=np.float64), np.zeros(nu.shape, dtype=np.float64)
+    rc = h.tsamd_ld_statistics(_dp(nu), _up(cn), nu.shape[0], nu.shape[1] - 1, _dp(r), _dp(p))
+    if rc != 0:
+        raise _lib.TsamdError(rc, h.tsamd_last_error(None).decode())
+    return r, p
+
+
+def ld_prune(r, r2_max):
+    """bool [n_locs]: the positions an LD pruning of the band r [n_locs][window + 1] keeps -- in ascending order, a position is
+    dropped if and only if a KEPT position at most window before it has r^2 > r2_max with it -- tsamd_ld_prune.  No device work."""
+    h = _lib.load()
+    ra = np.ascontiguousarray(r, dtype=np.float64)
+    if ra.ndim != 2 or ra.shape[1] < 1:
+        raise ValueError("r must be a band [n_locs][window + 1]")
+    keep = np.zeros(ra.shape[0], dtype=np.uint8)
+    rc = h.tsamd_ld_prune(_dp(ra), ra.shape[0], ra.shape[1] - 1, float(r2_max), keep.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise _lib.TsamdError(rc, h.tsamd_last_error(None).decode())
+    return keep.astype(bool)
+
+
 class Engine:
     def __init__(self, n, l, k, device=0, rank=0, world=1, flags=0, **overrides):
         self.h = _lib.load()
@@ -346,6 +375,23 @@ class Engine:
         if t is not None:
             out.update(trait_sums=ts, trait_counts=tc)
         return out
+
+    def ld(self, locs=None, window=64):
+        """structure-adjusted LD of the listed locations (None: every location) at most `window` list positions apart, over
+        this engine's shard -- tsamd_ld: dict(num, cnt), bands [n_locs][window + 1] whose column d of row i is the pair
+        (i, i + d).  Both are plain sums: add the shards' bands, then ld_statistics gives r and p and ld_prune the positions
+        to keep.  Changes no state."""
+        if locs is None:
+            a, n_locs = None, self.l
+        else:
+            a = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = a.size
+        window = int(window)
+        cols = window + 1 if 0 <= window <= _lib.LD_MAX_WINDOW else 1  # (a bad window is the library's to refuse)
+        num = np.zeros((n_locs, cols), dtype=np.float64)
+        cnt = np.zeros((n_locs, cols), dtype=np.uint32)
+        self._check(self.h.tsamd_ld(self.ctx, None if a is None else _up(a), n_locs, window & 0xffffffff, _dp(num), _up(cnt)))
+        return dict(num=num, cnt=cnt)
 
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
