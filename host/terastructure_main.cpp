@@ -160,6 +160,8 @@ struct Options {
   double ld_r2 = 0.2;           // -ld-r2: pruning drops a location whose r^2 with a kept one inside the window exceeds this
   double ld_min = 0.05;         // -ld-min: pairs with a smaller r^2 are not listed in ld.txt
   uint32_t ld_rows = 0;         // -ld-rows: rows of the band the host holds at a time (0: as many as 256 MB hold)
+  bool theta_se = false;        // extension: standard errors of the final theta, lambda taken as known (theta_se.txt)
+  uint32_t theta_se_rows = 65536;  // -theta-se-rows: individuals per tsamd_theta_info call (what the host holds at a time)
 };
 
 struct Timing {
@@ -176,6 +178,8 @@ struct Timing {
   double ld = 0;    // -ld: tsamd_ld over all locations and writing its files
   uint64_t ld_pairs = 0;
   uint32_t ld_kept = 0;
+  double theta_se = 0;  // -theta-se: tsamd_theta_info over all locations, tsamd_theta_se and writing theta_se.txt
+  uint32_t theta_se_na = 0;
   uint32_t logls = 0;
 };
 
@@ -384,7 +388,11 @@ void usage() {
           "\t\t\t window exceeds this (default 0.2)\n"
           "\t-ld-min <r2>\t -ld: lowest r2 listed in ld.txt (default 0.05; 0 lists every pair of the band)\n"
           "\t-ld-rows <rows>\t -ld: locations whose rows of the band the host holds at a time (default: as many as 256 MB\n"
-          "\t\t\t of host memory hold, at least 4096); the files do not depend on it beyond the rounding of r\n");
+          "\t\t\t of host memory hold, at least 4096); the files do not depend on it beyond the rounding of r\n"
+          "\t-theta-se\t with the final model (a plain run, -resume or -project): standard errors of theta from the observed\n"
+          "\t\t\t information over all locations, lambda taken as known.  Writes theta_se.txt: one line per\n"
+          "\t\t\t individual in theta.txt's order, K values; NA where an individual's theta is not identified\n"
+          "\t-theta-se-rows <n>\t -theta-se: individuals per call, whose K (K + 1) / 2 doubles each the host holds (default 65536)\n");
   fflush(stdout);
 }
 
@@ -863,6 +871,8 @@ void write_timing(Run &r) {
   if (r.o.scan) fprintf(f, "scan (-scan): %.3f (%u locations%s)\n", t.scan, r.o.l, r.o.pheno.empty() ? "" : ", with a trait");
   if (r.o.ld_set)
     fprintf(f, "ld (-ld): %.3f (window %u, %llu pairs listed, %u of %u locations kept)\n", t.ld, r.o.ld, (unsigned long long)t.ld_pairs, t.ld_kept, r.o.l);
+  if (r.o.theta_se)
+    fprintf(f, "theta standard errors (-theta-se): %.3f (%u individuals, %u not identified)\n", t.theta_se, r.o.n, t.theta_se_na);
   fprintf(f, "total: %u\n", r.duration());
   fclose(f);
 }
@@ -870,6 +880,7 @@ void write_timing(Run &r) {
 void kinship(Run &r);  // (-kinship, below)
 void scan(Run &r);     // (-scan, below)
 void ld(Run &r);       // (-ld, below)
+void theta_se(Run &r); // (-theta-se, below)
 
 // -project: the checkpoint's lambda into every context in chunks, tsamd_fold_in over all locations from gamma = 1 (no
 // validation sample is drawn: every stored genotype counts), then theta.txt / gamma.txt through the usual writer and
@@ -912,6 +923,7 @@ void project(Run &r, const ckpt::Buf &loc) {
   if (!o.kinship.empty()) kinship(r);  // (the folded-in theta against the file's lambda)
   if (o.scan) scan(r);                 // likewise
   if (o.ld_set) ld(r);                 // likewise
+  if (o.theta_se) theta_se(r);         // likewise: the standard errors of the projected cohort
   finish_saves(r);
   write_timing(r);
   printf("+ done: %u updates, %u of %u individuals converged\n", r.tm.project_iters_run, r.tm.project_converged, o.n);
@@ -1011,6 +1023,59 @@ void kinship(Run &r) {
   fclose(fi);
   r.tm.kinship += sw.lap();
   r.lerr("kinship of %u individuals: %u pairs at or above %g", m, r.tm.kinship_pairs, o.kinship_min);
+}
+
+// -theta-se: the observed information of every individual over all l locations under the state of the final save_model
+// (tsamd_theta_info, every device its own shard, -theta-se-rows individuals per call so that the host holds that many rows of
+// K (K + 1) / 2 doubles), tsamd_theta_se on each batch; theta_se.txt has one line per individual in theta.txt's order: the K
+// standard errors, tab-separated, "%.8f" through fmt_fixed8, NA for every value of a row that is not identified
+void theta_se(Run &r) {
+  Stopwatch sw;
+  const Options &o = r.o;
+  const uint32_t K = o.k, P = TSAMD_INFO_PACKED(K);
+  FILE *f = fopen(r.file_str("/theta_se.txt").c_str(), "w");
+  if (!f) {
+    r.lerr("cannot open theta_se.txt:%s\n", strerror(errno));
+    exit(-1);
+  }
+  const uint32_t rows = std::max<uint32_t>(1u, std::min(o.theta_se_rows, o.n));
+  std::vector<double> info((size_t)rows * P), se((size_t)rows * K);
+  std::vector<uint8_t> status(rows);
+  std::vector<uint32_t> ids(rows);
+  std::vector<char> buf((size_t)K * (tsfmt::kMaxLen + 1) + 8);
+  for (size_t i = 0; i < r.ctxs.size(); ++i) {  // shards in rank order: individuals ascending
+    uint32_t b, c;
+    shard_span(r, i, b, c);
+    r.ctx = r.ctxs[i];
+    for (uint32_t n0 = 0; n0 < c; n0 += rows) {
+      const uint32_t m = std::min(rows, c - n0);
+      for (uint32_t j = 0; j < m; ++j) ids[j] = b + n0 + j;
+      // (the shard's first m individuals go without a list: the columns are then read coalesced; the same bits either way)
+      TS(r, tsamd_theta_info(r.ctx, n0 == 0 ? nullptr : ids.data(), m, nullptr, o.l, info.data(), nullptr));
+      if (tsamd_theta_se(info.data(), m, K, se.data(), nullptr, status.data()) != TSAMD_OK) {
+        r.lerr("tsamd_theta_se: %s\n", tsamd_last_error(nullptr));
+        exit(-1);
+      }
+      for (uint32_t j = 0; j < m; ++j) {
+        char *p = buf.data();
+        for (uint32_t k = 0; k < K; ++k) {
+          if (k) *p++ = '\t';
+          if (status[j]) {
+            *p++ = 'N', *p++ = 'A';
+          } else {
+            p = tsfmt::fmt_fixed8(p, se[(size_t)j * K + k]);
+          }
+        }
+        *p++ = '\n';
+        fwrite(buf.data(), 1, (size_t)(p - buf.data()), f);
+        r.tm.theta_se_na += status[j] ? 1u : 0u;
+      }
+    }
+  }
+  r.ctx = r.ctxs[0];
+  fclose(f);
+  r.tm.theta_se += sw.lap();
+  r.lerr("standard errors of theta: %u individuals, %u not identified", o.n, r.tm.theta_se_na);
 }
 
 // -pheno: reads the trait -- one value per line in theta.txt's order, NA or nan for an individual that is not phenotyped --
@@ -1505,6 +1570,10 @@ int main(int argc, char **argv) {
     } else if (!strcmp(a, "-ld-rows")) {
       o.ld_rows = (uint32_t)std::max(0, atoi(need(a)));
       o.ld_rows_set = true;
+    } else if (!strcmp(a, "-theta-se")) {
+      o.theta_se = true;
+    } else if (!strcmp(a, "-theta-se-rows")) {
+      o.theta_se_rows = (uint32_t)std::max(0, atoi(need(a)));
     } else {
       fprintf(stdout, "error: unknown option %s\n", a);
       exit(-1);
@@ -1601,6 +1670,18 @@ int main(int argc, char **argv) {
     }
     if (o.ld_rows_set && o.ld_rows == 0) {
       fprintf(stderr, "error: -ld-rows needs at least 1 location\n");
+      return -1;
+    }
+  }
+
+  // -theta-se: likewise
+  if (o.theta_se) {
+    if (o.compute_beta || o.ingest_only) {
+      fprintf(stderr, "error: -theta-se evaluates a run's final model; it does not go with %s\n", o.compute_beta ? "-compute-beta" : "-ingest-only");
+      return -1;
+    }
+    if (o.theta_se_rows == 0) {
+      fprintf(stderr, "error: -theta-se-rows needs at least 1 individual\n");
       return -1;
     }
   }
@@ -1802,6 +1883,7 @@ int main(int argc, char **argv) {
   if (!o.kinship.empty()) kinship(r);     // likewise
   if (o.scan) scan(r);                    // likewise
   if (o.ld_set) ld(r);                    // likewise
+  if (o.theta_se) theta_se(r);            // likewise
   finish_saves(r);  // gamma.txt / theta.txt complete and closed before the process ends
   write_timing(r);
   destroy_all(r);

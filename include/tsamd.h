@@ -75,7 +75,10 @@ typedef struct tsamd_config {
                                         (locations per internal chunk of tsamd_snp_scan, whose segment count TSAMD_TEST_MAX_WORKGROUPS
                                         sets as for the other sweeps), TSAMD_TEST_LD_CHUNK (locations per internal chunk of tsamd_ld,
                                         rounded up to whole tiles of 64) and TSAMD_TEST_LD_BLOCK (individuals per internal block of
-                                        tsamd_ld, whose segment count TSAMD_TEST_MAX_WORKGROUPS sets as for the other sweeps) */
+                                        tsamd_ld, whose segment count TSAMD_TEST_MAX_WORKGROUPS sets as for the other sweeps),
+                                        TSAMD_TEST_INFO_CHUNK (locations per internal chunk of tsamd_theta_info) and
+                                        TSAMD_TEST_INFO_BLOCK (individuals per internal block of tsamd_theta_info, rounded up to a
+                                        multiple of 4; its segment count TSAMD_TEST_MAX_WORKGROUPS sets likewise) */
 
 int tsamd_abi_version(void);
 void tsamd_default_config(tsamd_config *cfg, uint32_t n, uint32_t l, uint32_t k);
@@ -326,6 +329,49 @@ int tsamd_ld_statistics(const double *num, const uint32_t *cnt, uint32_t n_locs,
  * KEPT position j in [i - window, i) has r[j][i - j]^2 > r2_max; otherwise keep[i] = 1.  No context, no device work.
  * TSAMD_EINVAL for n_locs == 0, a NULL r or keep, or an r2_max that is negative or not finite. */
 int tsamd_ld_prune(const double *r, uint32_t n_locs, uint32_t window, double r2_max, uint8_t *keep /* [n_locs] */);
+
+/* The information matrices of theta: the uncertainty of the fitted admixture proportions, individual by individual; changes no
+ * state (gamma, w, lambda, c_n, counters, the pending step and held-out folds stay as they are).  With lambda held fixed the
+ * individuals are independent, and the log-likelihood of individual n in theta is sum_j y log q + (2 - y) log(1 - q) with
+ * q = sum_k Ebeta[j][k] * Etheta[n][k].  Its negative Hessian is
+ *   H_n = sum_j c(n,j) b_j b_j^T,   b_j = Ebeta[j][.]   (K x K, symmetric, positive semi-definite, every entry >= 0),
+ *   c_obs = y / q^2 + (2 - y) / (1 - q)^2   (info_obs: the observed information),
+ *   c_exp = 2 / (q (1 - q))                 (info_exp: the expected information),
+ * returned PACKED: P = TSAMD_INFO_PACKED(k) doubles per individual, entry (a <= b) at a*k - a*(a-1)/2 + (b - a).
+ *  - q comes from the values tsamd_get_ebeta and tsamd_get_theta return at that moment: a pending gamma step stays pending.
+ *  - A stored code of 01 contributes nothing: missing entries, entries held out by tsamd_set_heldout, padding.  So does an entry
+ *    whose q is not inside (0, 1).
+ *  - indivs are GLOBAL ids inside the shard, in any order; a repeated id is a row of its own; NULL means the first m individuals
+ *    of the shard.
+ *  - locs == NULL means locations 0 .. n_locs-1 (n_locs <= l); a repeated location counts again.
+ *  - Synchronous; settles the context first like every getter.
+ *  - No floating-point atomics, a fixed summation order: two identical calls give identical bits.  An individual's row is the
+ *    same bits wherever it stands in a list of the same length, and a repeated id gives two identical rows.  A row may depend on
+ *    m and on how the library cuts the list into chunks, blocks and segments -- by rounding only.
+ *  - On a sharded context every rank answers for its own shard: no exchange is involved.
+ *  - The outputs are sums over the locations: the caller may add the rows of calls over disjoint location lists.
+ *  - Each output may be NULL, not both.  TSAMD_EINVAL for m == 0, n_locs == 0, a location >= l, an id outside the shard, or both
+ *    outputs NULL.  Every k the context accepts is served (P = 8256 at k = 128).
+ *  - The device scratch is bounded whatever m is: the library takes the list in blocks of individuals (at most 8192, fewer at a
+ *    large k) and copies each block's rows out.
+ * c is computed once per entry (ts_info_coef); the products C BB run on the matrix cores (v_mfma_f64_16x16x4_f64,
+ * csrc/tsamd_info_kernels.h). */
+#define TSAMD_INFO_PACKED(k) ((k) * ((k) + 1u) / 2u)   /* entry (a <= b) at a*k - a*(a-1)/2 + (b - a) */
+int tsamd_theta_info(tsamd_ctx *ctx, const uint32_t *indivs, uint32_t m, const uint32_t *locs, uint32_t n_locs,
+                     double *info_obs /* [m][P], may be NULL */, double *info_exp /* [m][P], may be NULL */);
+/* Standard errors and covariance of theta on the simplex from information matrices of tsamd_theta_info (either kind; rows of
+ * calls over disjoint location lists added by the caller).  Takes no context and does no device work: it runs without a GPU.
+ * Per individual: M = Z^T H Z with Z the basis that drops the last component (M_ab = H_ab - H_ak' - H_k'b + H_k'k', k' = k - 1,
+ * a, b < k - 1); Cholesky of M without pivoting; cov = Z M^-1 Z^T, packed like the input (its rows sum to zero by construction);
+ * se_a = sqrt(cov_aa).  k = 1 gives se = 0, cov = 0 and status 0.  Where a pivot is not above 1e-12 times its own original
+ * diagonal entry the row is not identified (fewer stored loci than k - 1, duplicated populations, an all-zero row): status = 1
+ * and se and cov of that row are NaN.  TSAMD_EINVAL for m == 0, k == 0, k > TSAMD_MAX_K, or a NULL info or se (the message:
+ * tsamd_last_error(NULL)).
+ * What the number is: the asymptotic plug-in standard error of the maximum-likelihood theta at the fitted theta, with lambda
+ * taken as known.  What it is not: it carries no uncertainty of lambda, and it is meaningful at interior theta -- on the boundary
+ * of the simplex (a component at or near 0) the normal approximation fails and the number is conservative advice at best. */
+int tsamd_theta_se(const double *info /* [m][P] */, uint32_t m, uint32_t k,
+                   double *se /* [m][k] */, double *cov /* [m][P], may be NULL */, uint8_t *status /* [m], may be NULL */);
 
 /* ---- multi-GPU: individuals sharded, lambda_t all-reduced per pass over RCCL ----
  * rank 0 calls tsamd_comm_unique_id and ships the bytes to every rank (any

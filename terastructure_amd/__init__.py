@@ -6,4 +6,4 @@ tests/, bench.py and __graft_entry__.py.
 """
 from ._lib import (Config, TsamdError, load, lib_path, FLAG_SPLIT_EPILOGUE, FLAG_NO_GRAPH, FLAG_TEST_HOOKS,  # noqa: F401
                    LAUNCH_PER_PASS, LAUNCH_PER_SNP, LAUNCH_PER_SCHEDULE)
-from .engine import Engine, ld_prune, ld_statistics, scan_statistics, shard_range  # noqa: F401
+from .engine import Engine, info_unpack, ld_prune, ld_statistics, scan_statistics, shard_range, theta_se  # noqa: F401

@@ -81,6 +81,8 @@ SYMBOLS = {
     "tsamd_ld": (_int, [_vp, _pu32, _u32, _u32, _pd, _pu32]),
     "tsamd_ld_statistics": (_int, [_pd, _pu32, _u32, _u32, _pd, _pd]),
     "tsamd_ld_prune": (_int, [_pd, _u32, _u32, _dbl, _pu8]),
+    "tsamd_theta_info": (_int, [_vp, _pu32, _u32, _pu32, _u32, _pd, _pd]),
+    "tsamd_theta_se": (_int, [_pd, _u32, _u32, _pd, _pd, _pu8]),
     "tsamd_state_sizes": (_int, [_vp, _pu64, _pu64]),
     "tsamd_state_export": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "tsamd_state_import": (_int, [_vp, _vp, _u64, _vp, _u64]),

@@ -81,6 +81,8 @@ def _units():
     units.append((os.path.join(OBJ_DIR, "scan.o"), os.path.join(CSRC, "tsamd_scan.hip"), []))
     # tsamd_ld's kernels, likewise (csrc/tsamd_ld.hip)
     units.append((os.path.join(OBJ_DIR, "ld.o"), os.path.join(CSRC, "tsamd_ld.hip"), []))
+    # tsamd_theta_info's kernels, likewise (csrc/tsamd_info.hip)
+    units.append((os.path.join(OBJ_DIR, "info.o"), os.path.join(CSRC, "tsamd_info.hip"), []))
     return units
 
 

@@ -28,6 +28,7 @@
 #include "tsamd_loglik_plan.h"
 #include "tsamd_foldin_plan.h"
 #include "tsamd_kin_plan.h"
+#include "tsamd_info_plan.h"
 #include "tsamd_ld_plan.h"
 #include "tsamd_scan_plan.h"
 #include "tsamd_unit.h"
@@ -157,6 +158,10 @@ struct tsamd_ctx {
   // kLdScratchBound bytes each), the chunk's rows of the band ([chunk][window + 1] num, then cnt) and its locations with their
   // overlap; allocated on first use
   DevBuf d_ld_zm, d_ld_part, d_ld_acc, d_ld_band, d_ld_locs;
+  // tsamd_theta_info: c_obs and c_exp of a chunk, its BB, the segments' partial tiles, a block's accumulators, its two sets of rows
+  // (info_geometry: at most kInfoScratchBound bytes each), the block's individuals [bpad] and then the chunk's locations;
+  // allocated on first use
+  DevBuf d_info_coef, d_info_bb, d_info_part, d_info_acc, d_info_rows, d_info_idx;
   ncclComm_t comm = nullptr;
   Xchg *xchg = nullptr;                    // peer-to-peer exchange buffer (fine-grained, IPC-exported)
   std::vector<void *> peer_maps;           // hipIpcOpenMemHandle results to close
@@ -567,7 +572,7 @@ int check_locs(tsamd_ctx *c, uint32_t first_loc, uint32_t n_locs) {
   return TSAMD_OK;
 }
 
-// ---- the front end of the analysis calls: tsamd_train_loglik, tsamd_fold_in, tsamd_kinship, tsamd_snp_scan, tsamd_ld ---------------------
+// ---- the front end of the analysis calls: tsamd_train_loglik, tsamd_fold_in, tsamd_kinship, tsamd_snp_scan, tsamd_ld, tsamd_theta_info ---
 
 // the list of locations such a call takes (locs == NULL: locations 0 .. n_locs - 1)
 int check_loc_list(tsamd_ctx *c, const uint32_t *locs, uint32_t n_locs) {
@@ -597,7 +602,7 @@ int runtime_k_theta(tsamd_ctx *c, const double **thn) {
   return TSAMD_OK;
 }
 
-// The chunk loop of train_loglik, kinship, snp_scan and ld.  The listed locations go chunk after chunk: a chunk's locations --
+// The chunk loop of train_loglik, kinship, snp_scan, ld and theta_info.  The listed locations go chunk after chunk: a chunk's locations --
 // and up to `halo` of those that follow them (ld's overlap; 0 for the others) -- are staged and uploaded to d_locs,
 // enqueue(off, len) launches its kernels, its results -- row_bytes per listed location from dev to host, for each of outs --
 // are fetched, the stream is waited for (the staging vector and the hosts' buffers are reused) and collect(off, len) takes the
@@ -695,7 +700,8 @@ void tsamd_destroy(tsamd_ctx *c) {
   for (DevBuf *b : {&c->d_hids, &c->d_hy, &c->d_hterms, &c->d_hreq, &c->d_fold_ids, &c->d_fold_orig, &c->d_hsums, &c->d_ll_part, &c->d_ll_chunk,
                     &c->d_ll_acc, &c->d_ll_thn, &c->d_fi_part, &c->d_fi_ind, &c->d_fi_locs, &c->d_kin_rs, &c->d_kin_part, &c->d_kin_acc,
                     &c->d_kin_idx, &c->d_scan_part, &c->d_scan_chunk, &c->d_scan_trait, &c->d_ld_zm, &c->d_ld_part,
-                    &c->d_ld_acc, &c->d_ld_band, &c->d_ld_locs})
+                    &c->d_ld_acc, &c->d_ld_band, &c->d_ld_locs, &c->d_info_coef, &c->d_info_bb, &c->d_info_part, &c->d_info_acc,
+                    &c->d_info_rows, &c->d_info_idx})
     b->free();
   if (c->h_stage) hipHostFree(c->h_stage);
   c->d_state.free();
@@ -2052,6 +2058,79 @@ int tsamd_ld_prune(const double *r, uint32_t n_locs, uint32_t window, double r2_
   if (!r || !keep) return fail(nullptr, TSAMD_EINVAL, "r and keep must not be NULL");
   if (!(r2_max >= 0.0) || !std::isfinite(r2_max)) return fail(nullptr, TSAMD_EINVAL, "r2_max must be finite and not negative");
   ld_prune(r, n_locs, window, r2_max, keep);
+  return TSAMD_OK;
+}
+
+// Block after block of listed individuals; per block chunk after chunk of locations (for_each_chunk): c_obs, c_exp and BB of the
+// chunk once (ts_info_coef, ts_info_outer), the two products tile by tile on the matrix cores (ts_info_gemm, ts_info_finish:
+// csrc/tsamd_info_kernels.h); after the last chunk the block's rows are copied out.  Reads the state only.
+int tsamd_theta_info(tsamd_ctx *c, const uint32_t *indivs, uint32_t m, const uint32_t *locs, uint32_t n_locs, double *info_obs, double *info_exp) {
+  CHECK_CTX(c);
+  static_assert(TSAMD_MAX_K == kInfoMaxK && TSAMD_INFO_PACKED(TSAMD_MAX_K) == info_packed(kInfoMaxK), "the header's packing is the plan's");
+  if (m == 0) return fail(c, TSAMD_EINVAL, "m must be positive");
+  if (n_locs == 0) return check_loc_list(c, locs, n_locs);
+  if (!info_obs && !info_exp) return fail(c, TSAMD_EINVAL, "info_obs and info_exp are both NULL");
+  if (int rc = check_loc_list(c, locs, n_locs)) return rc;
+  if (!indivs && m > c->n_local) return fail(c, TSAMD_EINVAL, "m = %u exceeds the shard's %u individuals (indivs == NULL: its first m)", m, c->n_local);
+  if (indivs)
+    for (uint32_t i = 0; i < m; ++i)
+      if (indivs[i] < c->n_begin || indivs[i] - c->n_begin >= c->n_local)
+        return fail(c, TSAMD_EINVAL, "indivs[%u] = %u is outside the shard [%u, %u)", i, indivs[i], c->n_begin, c->n_begin + c->n_local);
+  HIP_TRY(c, hipSetDevice(c->dev));
+  SETTLE(c);
+  const InfoGeom g = info_geometry(m, c->cfg.k, n_locs, device_width(c), test_hook(c, "TSAMD_TEST_INFO_CHUNK"), test_hook(c, "TSAMD_TEST_INFO_BLOCK"));
+  const uint32_t chunk4 = info_round_step(g.chunk);
+
+  HIP_TRY(c, c->d_info_coef.reserve((size_t)info_coef_bytes(g)));
+  HIP_TRY(c, c->d_info_bb.reserve((size_t)info_bb_bytes(g)));
+  HIP_TRY(c, c->d_info_part.reserve((size_t)info_part_bytes(g)));
+  HIP_TRY(c, c->d_info_acc.reserve((size_t)info_acc_bytes(g)));
+  HIP_TRY(c, c->d_info_rows.reserve((size_t)info_rows_bytes(g)));
+  HIP_TRY(c, c->d_info_idx.reserve(((size_t)g.bpad + g.chunk) * sizeof(uint32_t)));
+  uint32_t *d_ids = c->d_info_idx.as<uint32_t>(), *d_locs = d_ids + g.bpad;
+  double *d_obs = c->d_info_rows.as<double>(), *d_exp = d_obs + (size_t)g.block * g.p;
+
+  InfoArgs a{};
+  a.bed = c->p.bed, a.colstride = c->p.colstride, a.gam = c->p.gam, a.lam = c->p.lam, a.ids = indivs ? d_ids : nullptr, a.locs = d_locs;
+  a.npad = c->npad, a.n_local = c->n_local, a.K = g.k, a.P = g.p, a.ppad = g.ppad, a.ptiles = g.ptiles;
+  a.cobs = c->d_info_coef.as<double>(), a.cexp = a.cobs + (size_t)chunk4 * g.bpad, a.bb = c->d_info_bb.as<double>();
+  a.part = c->d_info_part.as<double>(), a.acc = c->d_info_acc.as<double>();
+  std::vector<uint32_t> h_ids(indivs ? g.bpad : 0u);
+  for (uint32_t i0 = 0; i0 < m; i0 += g.block) {
+    a.ind0 = i0, a.blen = std::min(g.block, m - i0), a.bpad = info_round_tile(a.blen);
+    const uint32_t tiles = a.bpad / kInfoTile * g.ptiles;
+    if (indivs) {
+      for (uint32_t i = 0; i < a.bpad; ++i) h_ids[i] = i < a.blen ? indivs[i0 + i] - c->n_begin : 0xffffffffu;
+      HIP_TRY(c, hipMemcpyAsync(d_ids, h_ids.data(), (size_t)a.bpad * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemsetAsync(a.acc, 0, (size_t)tiles * kInfoTileBytes, c->stream));
+    const int rc = for_each_chunk(
+        c, locs, n_locs, g.chunk, 0u, d_locs, {},
+        [&](uint32_t, uint32_t len) {
+          a.len = len, a.len4 = info_round_step(len);
+          const KinSegs sg = info_segments(g, len);
+          info_launch_coef(a, c->stream);
+          for (uint32_t t0 = 0; t0 < tiles; t0 += g.tiles_per_launch) info_launch_tiles(a, t0, std::min(g.tiles_per_launch, tiles - t0), sg, c->stream);
+        },
+        [](uint32_t, uint32_t) {});  // (the accumulators stay on the device until the block's last chunk)
+    if (rc) return rc;
+    info_launch_rows(a, d_obs, d_exp, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    const size_t bytes = (size_t)a.blen * g.p * sizeof(double);
+    if (info_obs) HIP_TRY(c, hipMemcpyAsync(info_obs + (size_t)i0 * g.p, d_obs, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (info_exp) HIP_TRY(c, hipMemcpyAsync(info_exp + (size_t)i0 * g.p, d_exp, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return TSAMD_OK;
+}
+
+// no context, no device work: standard errors and covariance of theta on the simplex from information matrices (theta_se,
+// csrc/tsamd_info_plan.h)
+int tsamd_theta_se(const double *info, uint32_t m, uint32_t k, double *se, double *cov, uint8_t *status) {
+  if (m == 0) return fail(nullptr, TSAMD_EINVAL, "m must be positive");
+  if (k == 0 || k > TSAMD_MAX_K) return fail(nullptr, TSAMD_EINVAL, "k = %u must lie in 1 .. TSAMD_MAX_K = %u", k, (uint32_t)TSAMD_MAX_K);
+  if (!info || !se) return fail(nullptr, TSAMD_EINVAL, "info and se must not be NULL");
+  theta_se(info, m, k, se, cov, status);
   return TSAMD_OK;
 }
 

@@ -92,6 +92,44 @@ def ld_prune(r, r2_max):
     return keep.astype(bool)
 
 
+def info_packed(k):
+    """P = k (k + 1) / 2: the packed length of a symmetric k x k matrix -- TSAMD_INFO_PACKED"""
+    return k * (k + 1) // 2
+
+
+def info_unpack(packed, k):
+    """[m][k][k], symmetric, from packed rows [m][P] of Engine.theta_info or theta_se's cov: entry (a <= b) of a row is at
+    a k - a (a - 1) / 2 + (b - a)."""
+    pa = np.asarray(packed, dtype=np.float64)
+    if pa.ndim != 2 or pa.shape[1] != info_packed(k):
+        raise ValueError(f"packed must be [m][{info_packed(k)}]")
+    a, b = np.triu_indices(k)  # (row by row: the packed order)
+    out = np.zeros((pa.shape[0], k, k), dtype=np.float64)
+    out[:, a, b] = pa
+    out[:, b, a] = pa
+    return out
+
+
+def theta_se(info, k):
+    """dict(se [m][k], cov [m][P] packed, status [m]) from information matrices [m][P] of Engine.theta_info (either kind; rows
+    over disjoint location lists added by the caller) -- tsamd_theta_se: the asymptotic plug-in standard errors of theta on
+    the simplex with lambda taken as known.  status 1 marks a row that is not identified: its se and cov are NaN.  No device
+    work: runs without a GPU."""
+    h = _lib.load()
+    k = int(k)
+    ia = np.ascontiguousarray(info, dtype=np.float64)
+    if ia.ndim != 2 or not 1 <= k <= 128 or ia.shape[1] != info_packed(k):
+        raise ValueError("info must be [m][k (k + 1) / 2] with 1 <= k <= 128")
+    m = ia.shape[0]
+    se = np.zeros((m, k), dtype=np.float64)
+    cov = np.zeros(ia.shape, dtype=np.float64)
+    status = np.zeros(m, dtype=np.uint8)
+    rc = h.tsamd_theta_se(_dp(ia), m, k, _dp(se), _dp(cov), status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise _lib.TsamdError(rc, h.tsamd_last_error(None).decode())
+    return dict(se=se, cov=cov, status=status)
+
+
 class Engine:
     def __init__(self, n, l, k, device=0, rank=0, world=1, flags=0, **overrides):
         self.h = _lib.load()
@@ -392,6 +430,27 @@ class Engine:
         cnt = np.zeros((n_locs, cols), dtype=np.uint32)
         self._check(self.h.tsamd_ld(self.ctx, None if a is None else _up(a), n_locs, window & 0xffffffff, _dp(num), _up(cnt)))
         return dict(num=num, cnt=cnt)
+
+    def theta_info(self, indivs=None, locs=None):
+        """information matrices of theta of the listed individuals (GLOBAL ids inside this engine's shard; None: the whole
+        shard) over locs (None: every location) -- tsamd_theta_info: dict(obs, exp), each [m][P] packed (info_unpack), the
+        observed and the expected information with lambda held fixed.  Both are plain sums over the locations; theta_se turns
+        either into standard errors.  Changes no state."""
+        if indivs is None:
+            ia, m = None, self.shard_count
+        else:
+            ia = np.ascontiguousarray(indivs, dtype=np.uint32)
+            m = ia.size
+        if locs is None:
+            la, n_locs = None, self.l
+        else:
+            la = np.ascontiguousarray(locs, dtype=np.uint32)
+            n_locs = la.size
+        obs = np.zeros((m, info_packed(self.k)), dtype=np.float64)
+        exp = np.zeros((m, info_packed(self.k)), dtype=np.float64)
+        self._check(self.h.tsamd_theta_info(self.ctx, None if ia is None else _up(ia), m, None if la is None else _up(la), n_locs,
+                                            _dp(obs), _dp(exp)))
+        return dict(obs=obs, exp=exp)
 
     # -- the full state: save / restore ------------------------------------------
     def state_sizes(self):
