@@ -159,10 +159,18 @@ __device__ __forceinline__ unsigned long long fail_code(uint32_t tag, bool intac
 // One wave sweeps N row pairs of one column block: lane l, load i = granule col0 + l % 32 of row 2 i + (l >= 32);
 // rows >= row_limit do not exist, granules >= nvalid carry nothing.  Polls until every existing granule carries
 // `tag`; false when the bounded wait gave up (abort_word set, host told).
-template <int N, int SCOPE>
+// FULL (ts_schedule at K <= 8 on one GPU): when all 2 N rows and all 32 granules exist -- one uniform test before the
+// loop; the benchmark's 256 workgroups at K = 8 -- the low words are taken as loaded and only the tags are compared.  The
+// general loop ends every load with a select on `exists`, which the compiler sinks below the poll: 16 v_cndmask (16
+// cycles each for a lone wave) between a leader's last load and its row sum, with every workgroup waiting.
+template <int N, int SCOPE, bool FULL = false>
 __device__ __forceinline__ bool res_sweep(const unsigned long long *base, uint32_t stride, uint32_t col0, uint32_t tag, uint32_t nvalid,
                                           uint32_t row_limit, unsigned (&v)[N], unsigned long long *abort_word,
                                           unsigned long long *host_flag, unsigned long long code, unsigned long long ticks, uint32_t lane) {
+  if constexpr (FULL) {
+    if (row_limit < 2u * (uint32_t)N || nvalid < 32u)
+      return res_sweep<N, SCOPE, false>(base, stride, col0, tag, nvalid, row_limit, v, abort_word, host_flag, code, ticks, lane);
+  }
   const uint32_t c = lane & 31u;
   const unsigned long long t0 = wall_clock64();
   for (;;) {
@@ -170,7 +178,7 @@ __device__ __forceinline__ bool res_sweep(const unsigned long long *base, uint32
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const uint32_t row = 2u * (uint32_t)i + (lane >> 5);
-      const bool exists = c < nvalid && row < row_limit;
+      const bool exists = FULL || (c < nvalid && row < row_limit);
       const unsigned long long x = __hip_atomic_load(base + (size_t)row * stride + col0 + c, __ATOMIC_RELAXED, SCOPE);
       v[i] = exists ? (unsigned)x : 0u;
       ok &= !exists || (unsigned)(x >> 32) == tag;
@@ -292,7 +300,8 @@ __device__ __forceinline__ void res_post(unsigned long long *dst, uint32_t tag, 
 struct NoOverlap {
   __device__ __forceinline__ void operator()() const {}
 };
-template <int KT, int WR, int ONE = kResOneLevelGrid, class LAY = ResLay<KT>, class OV = NoOverlap>
+// FULL: the two-level sweeps of a one-GPU exchange take res_sweep's select-free path when all their rows and granules exist.
+template <int KT, int WR, int ONE = kResOneLevelGrid, class LAY = ResLay<KT>, bool FULL = false, class OV = NoOverlap>
 __device__ __forceinline__ bool res_exchange(ResXchg *xb, const DevParams &p, uint32_t tag, uint32_t width, double mine, uint32_t g, uint32_t m,
                                              uint32_t grid, double *s_tot /* [2][2K] */, int *s_alive /* [4], all 1 */, uint32_t tid,
                                              unsigned long long code, unsigned long long ticks, OV overlap = OV()) {
@@ -414,7 +423,7 @@ __device__ __forceinline__ bool res_exchange(ResXchg *xb, const DevParams &p, ui
       if (q < nblk) {
         const uint32_t region = q / RB, cb = q % RB, nvalid = min(32u, 2u * J - 32u * cb);
         unsigned v[kResMembers / 2];
-        alive = res_sweep<kResMembers / 2, __HIP_MEMORY_SCOPE_AGENT>(L::rows(xb, region, g, 0), GR, 32u * cb, tag, nvalid, members, v, &xb->abort_word,
+        alive = res_sweep<kResMembers / 2, __HIP_MEMORY_SCOPE_AGENT, FULL && WR == 0>(L::rows(xb, region, g, 0), GR, 32u * cb, tag, nvalid, members, v, &xb->abort_word,
                                                                      p.host_error, code, ticks, lane) && alive;
         const double s = res_sum<kResMembers / 2>(v, lane);
         if (lane < nvalid && !(lane & 1u)) {
@@ -507,7 +516,7 @@ __device__ __forceinline__ bool res_exchange(ResXchg *xb, const DevParams &p, ui
       double s;
       if constexpr (WR == 0) {
         unsigned v2[kResGroups / 2];
-        alive = res_sweep<kResGroups / 2, __HIP_MEMORY_SCOPE_AGENT>(L::sums(xb, region, tag & 1u, 0), GR, 32u * cb, tag, nvalid, groups, v2, &xb->abort_word,
+        alive = res_sweep<kResGroups / 2, __HIP_MEMORY_SCOPE_AGENT, FULL>(L::sums(xb, region, tag & 1u, 0), GR, 32u * cb, tag, nvalid, groups, v2, &xb->abort_word,
                                                                     p.host_error, code, ticks, lane) && alive;
         s = res_sum<kResGroups / 2>(v2, lane);
       } else if (p.xchg_gather_leaders == 0u || m == 0u) {
@@ -966,6 +975,13 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
 #define TSAMD_DIET 3
 #endif
   constexpr bool kDietSel = KT <= 8 && (TSAMD_DIET & 1) != 0, kDietConst = KT <= 8 && (TSAMD_DIET & 2) != 0;
+  // kXchgFull: the same kind of saving in a pass' exchange (profiles/k8_exchange_diet.md).  When every row and every
+  // granule of a sweep exists -- 32 members in the leader's group, 8 groups, K = 8 -- the poll compares tags and takes the
+  // words as loaded (res_sweep's FULL path): no select between a poll's last load and the sum it feeds.  One GPU, K <= 8.
+#ifndef TSAMD_XCHG_DIET  // (experiments, tools/variant.sh: bit 0 the select-free sweeps)
+#define TSAMD_XCHG_DIET 1
+#endif
+  constexpr bool kXchgFull = KT <= 8 && WR == 0 && (TSAMD_XCHG_DIET & 1) != 0;
   __shared__ __attribute__((aligned(16))) double s_ebw[kWaves][J];
   __shared__ double s_diffw[kWaves][J];
   __shared__ double s_red[kWaves * J];
@@ -1247,7 +1263,8 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
     }
     xcount += 1u;
     const uint32_t tag = xseq0 + xcount;
-    if (!res_exchange<KT, WR>(xb, p, tag, width, mine, g, m, gridDim.x, s_tot, s_alive, tid, fail_code(tag, false, par, serial), kResWaitTicks))
+    if (!res_exchange<KT, WR, kResOneLevelGrid, ResLay<KT>, kXchgFull>(xb, p, tag, width, mine, g, m, gridDim.x, s_tot, s_alive, tid,
+                                                                       fail_code(tag, false, par, serial), kResWaitTicks))
       return false;
 #ifdef TSAMD_SCHED_TIME
     const unsigned long long te0 = wall_clock64();
@@ -1353,12 +1370,14 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
       // selects this kernel only then), then the new weights.  An unobserved genotype takes the same instructions
       // with a step size of exactly 0: gamma keeps its bits (its update term is finite), the weights are recomputed
       // from the unchanged gamma, c_n does not count -- no select per value.
+      // (the lean form below everywhere but in the sharded full-size K <= 8 instantiations, which sit at 463 ... 499
+      // registers and were left alone.  The one-GPU full-size K <= 8 instantiation ran the literal form while the lean one
+      // spilled there; it no longer does.  TSAMD_LITERAL_STEP gives it that form back -- the bits of the tree before, for
+      // A/B runs and dump comparisons: profiles/k8_exchange_diet.md)
 #if defined(TSAMD_LITERAL_STEP)  // (experiments)
-      constexpr bool kLeanStep = false;
-#elif defined(TSAMD_LEAN_STEP)
-      constexpr bool kLeanStep = true;
-#else
       constexpr bool kLeanStep = PARTIAL || KT > 8;
+#else
+      constexpr bool kLeanStep = PARTIAL || KT > 8 || WR == 0;
 #endif
       constexpr bool kSbScalar = kRepl && BSC && TSAMD_GAMMA_SB_READLANE != 0;
       double sbs[kSbScalar ? J : 1];
@@ -1397,7 +1416,7 @@ __global__ __launch_bounds__(256, 1) void ts_schedule(Ctl *ctl_a, double *w_a, u
           const double c0 = (mom * s1) * inv, c1 = (dad * s0) * inv, keep = 1.0 - rho, ra = rho * p.alpha;
 #pragma unroll
           for (int k = 0; k < KT; ++k) gx[k] = fma(wx[k], fma(c0, sb(2 * k), c1 * sb(2 * k + 1)), fma(keep, gx[k], ra));
-        } else {  // (the literal form, seven instructions per population: the full-size K <= 8 instantiation spills with the other)
+        } else {  // (the literal form, seven instructions per population and two reciprocals: sharded full size at K <= 8, and TSAMD_LITERAL_STEP)
           const double c0 = mom * fast_rcp(s0), c1 = dad * fast_rcp(s1);
 #pragma unroll
           for (int k = 0; k < KT; ++k) {
