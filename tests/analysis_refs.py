@@ -1,5 +1,5 @@
-"""Extended-precision references, with derived error bounds, of the four analysis calls: tsamd_train_loglik, tsamd_snp_scan,
-tsamd_kinship and tsamd_fold_in.
+"""Extended-precision references, with derived error bounds, of five analysis calls: tsamd_train_loglik, tsamd_snp_scan,
+tsamd_kinship, tsamd_fold_in and tsamd_ld.
 
 Every function takes PLANTED inputs only -- the genotypes y [l][n] in {0, 1, 2, 3 = missing}, gamma [n][k], lambda [l][k][2],
 the held-out lists {location: global ids}, the trait, the id list -- and never a value read back from an engine, so a getter
@@ -19,7 +19,12 @@ u = 2^-53, not measured:
   * a sum of M terms adds M u sum |term|, whatever its order;
   * the per-location and per-individual sums of train_loglik and snp_scan carry a factor 4 on top, for the kernels' own
     summation order and multiply-add contraction; the kinship bound is the worst-order bound as it stands:
-    sum_j (|r_a| dr_b + |r_b| dr_a) + (J + 2) u sum_j |r_a r_b| for num, the same with s for den, the quotient rule for kin.
+    sum_j (|r_a| dr_b + |r_b| dr_a) + (J + 2) u sum_j |r_a r_b| for num, the same with s for den, the quotient rule for kin;
+  * tsamd_ld's z = r / sqrt(h) (0 where the entry is not stored or h <= 0) has absolute error
+    dz = dr / sqrt(h) + |z| ((c_q + d1) / 2 + 3 u): the error of r, half the relative error of h, then one rounding each for
+    the product 2 q (1 - q) behind the root, the root and the division; num of the pair of list positions (i, i + d) gets
+    the worst-order bound as it stands, like kinship's and without the factor 4:
+    sum_n (|z_i| dz_{i+d} + |z_{i+d}| dz_i) + (M + 2) u sum_n |z_i z_{i+d}|, M the shard's individuals; cnt is exact.
 An entry whose exact product C(2,y) q^y (1-q)^(2-y) lies in [1e-31, 1e-29] is refused: at the 1e-30 clamp of the
 log-likelihood term a rounding decides between two different terms and no bound holds.
 """
@@ -184,6 +189,42 @@ def kin_ref(y, gamma, lam, ids, held=None, locs=None, shard=None, entries=None):
     return dict(num=num, den=den, kin=kin), dict(num=bnum, den=bden, kin=bkin)
 
 
+def _band(full, window):
+    """[J][window + 1] of a [J][J] matrix: column d of row i is entry (i, i + d), 0 where i + d >= J"""
+    J = full.shape[0]
+    i = np.arange(J)[:, None]
+    j = i + np.arange(window + 1)[None, :]
+    return np.where(j < J, full[i, np.minimum(j, J - 1)], 0)
+
+
+def _band_of_products(a, b, window):
+    """[J][window + 1]: sum_n a(i, n) b(i + d, n) of a, b [J][M]; from the full product a b^T where the band covers most of it"""
+    J = a.shape[0]
+    reach = min(window, J - 1)
+    if 2 * (reach + 1) > J:
+        return _band(a @ b.T, window)
+    out = np.zeros((J, window + 1), dtype=np.result_type(a, b))
+    for d in range(reach + 1):
+        out[:J - d, d] = (a[:J - d] * b[d:]).sum(axis=1)
+    return out
+
+
+def ld_ref(y, gamma, lam, window, held=None, locs=None, shard=None, entries=None):
+    """(ref, bound): num, cnt (uint32), absn, bands [J][window + 1] whose column d of row i is the pair of list positions
+    (i, i + d), 0 where i + d >= J; bound has num"""
+    e = _entries(y, gamma, lam, held, locs, shard, entries)
+    ok = e.ok & (e.h > 0)
+    root = np.sqrt(np.where(ok, e.h, 1))
+    z = np.where(ok, e.r / root, 0)                                                   # [J][count]
+    dz = np.where(ok, e.dr / root + np.abs(z) * ((e.c_q + e.d1) / 2 + 3 * U), 0)
+    az = np.abs(z)
+    m = ok.astype(np.float64)                                                         # (0 / 1: the fp64 product is exact)
+    num, absn = _band_of_products(z, z, window), _band_of_products(az, az, window)
+    cnt = _band(m @ m.T, window).astype(np.uint32)
+    bnum = _band_of_products(az, dz, window) + _band_of_products(dz, az, window) + (z.shape[1] + 2) * U * absn
+    return dict(num=num, cnt=cnt, absn=absn), dict(num=bnum)
+
+
 def foldin_ref(y, gamma, lam, alpha, snapshots, held=None, locs=None, shard=None):
     """{i: dict(gamma [count][k], iters [count], change [count])} after i = each of `snapshots` updates at tol = 0, from
         w_k = exp(psi(gamma_k) - psi(sum_k gamma_k)),  eb = exp(psi(lambda) - psi(lambda0 + lambda1))
@@ -254,6 +295,21 @@ def compare_kin(got, ref, bound, limit=1.0):
     assert np.all(np.asarray(kin)[ref["den"] == 0] == 0.0)
     worst = max(ratio(num, ref["num"], bound["num"]), ratio(den, ref["den"], bound["den"]), ratio(kin, ref["kin"], bound["kin"]))
     assert worst <= limit, ("kinship", worst)
+    return worst
+
+
+def compare_ld(got, ref, bound, limit=1.0):
+    """got = dict(num, cnt): cnt byte for byte, the entries past the list's end exactly 0, every value finite"""
+    num, cnt = np.asarray(got["num"]), np.asarray(got["cnt"])
+    assert num.shape == ref["num"].shape and cnt.shape == ref["cnt"].shape and cnt.dtype == np.uint32
+    assert np.all(np.isfinite(num))
+    assert cnt.tobytes() == ref["cnt"].tobytes(), "cnt"
+    J, w1 = num.shape
+    past = np.add.outer(np.arange(J), np.arange(w1)) >= J
+    for a in (num, cnt, ref["num"], ref["cnt"]):
+        assert np.all(a[past] == 0), "an entry past the list's end"
+    worst = ratio(num, ref["num"], bound["num"])
+    assert worst <= limit, ("ld", worst)
     return worst
 
 

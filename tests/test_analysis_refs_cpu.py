@@ -1,6 +1,7 @@
 """tests/analysis_refs.py on its own: the references against a brute-force loop, and the derived bounds against a plain fp64
 numpy evaluation in the engine's order -- every value within HALF of its bound (the bounds are not too tight for a correct
-fp64 evaluation), and each of four subtle mutations of that evaluation outside a bound (they are not too loose to see one)."""
+fp64 evaluation), and each of four subtle mutations of that evaluation outside a bound (they are not too loose to see one).
+tsamd_ld (ld_ref, compare_ld) goes through the same three sections, with one mutation of its own: the band read one column off."""
 import hashlib
 import math
 
@@ -72,6 +73,21 @@ class Fp64:
             kin = np.where(den != 0.0, num / (4.0 * den), 0.0)
         return kin, num, den
 
+    def ld(self, locs, window):
+        """dict(num, cnt), bands [J][window + 1], in ld_terms' order: 2 q (1 - q), y - (q + q), one sqrt, one division"""
+        q, y = self.q(np.arange(len(self.ys)) if locs is None else locs)
+        h = 2.0 * q * (1.0 - q)
+        ok = (y != 3) & (h > 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = np.where(ok, (np.where(ok, y, 0) - (q + q)) / np.sqrt(h), 0.0)
+        m = ok.astype(np.float64)
+        J = z.shape[1]
+        num, cnt = np.zeros((J, window + 1)), np.zeros((J, window + 1))
+        for d in range(min(window, J - 1) + 1):
+            num[:J - d, d] = (z[:, :J - d] * z[:, d:]).sum(axis=0)
+            cnt[:J - d, d] = (m[:, :J - d] * m[:, d:]).sum(axis=0)
+        return dict(num=num, cnt=cnt.astype(np.uint32))
+
     def foldin(self, locs, iters):
         y = self.ys[locs].T
         mom, dad = np.where(y == 3, 0.0, y), np.where(y == 3, 0.0, 2.0 - y)
@@ -101,6 +117,16 @@ def compare_all(f, c, refs, shard=None, limit=0.5, iters=(1, 3)):
                  kin=ar.compare_kin(f.kin(c.ids, c.locs), *refs["kin"], limit=limit))
     worst["foldin"] = max(ar.compare_foldin(*f.foldin(c.locs, i), refs["foldin"][i], limit=limit) for i in iters)
     return worst
+
+
+def ld_refs(c, window, shard=None):
+    """{list: (ref, bound)} of the full list (None) and of c.locs, from one Entries"""
+    every = ar.Entries(c.y, c.gamma, c.lam, c.held, None, shard)
+    return {key: ar.ld_ref(c.y, c.gamma, c.lam, window, c.held, which, shard, entries=every) for key, which in (("all", None), ("list", c.locs))}
+
+
+def compare_ld_lists(f, c, refs, window, limit=0.5):
+    return max(ar.compare_ld(f.ld(which, window), *refs[key], limit=limit) for key, which in (("all", None), ("list", c.locs)))
 
 
 # -- 1. brute force ----------------------------------------------------------------------------------------------------------------
@@ -170,6 +196,29 @@ def test_the_references_equal_a_brute_force_loop():
     kin = np.array([[num[a, b] / (4 * den[a, b]) if den[a, b] > 0 else zero for b in range(m)] for a in range(m)], dtype=LD)
     for key, v in (("num", num), ("den", den), ("kin", kin)):
         assert ar.ratio(v, ref[key], bound[key]) <= tiny, key
+    # LD at window 3: individual after individual, pair after pair of list positions; the list's repeat (positions 2 and 3)
+    # is a pair of its own
+    w = 3
+    ldnum, ldabs, ldcnt = [[zero] * (w + 1) for _ in range(J)], [[zero] * (w + 1) for _ in range(J)], [[0] * (w + 1) for _ in range(J)]
+    for i in range(n):
+        zi = [(r[i][jj] / np.sqrt(2 * qof(i, loc) * (1 - qof(i, loc))) if stored(i, loc) else None) for jj, loc in enumerate(locs)]
+        for a in range(J):
+            for d in range(w + 1):
+                if a + d < J and zi[a] is not None and zi[a + d] is not None:
+                    ldnum[a][d] += zi[a] * zi[a + d]
+                    ldabs[a][d] += abs(zi[a] * zi[a + d])
+                    ldcnt[a][d] += 1
+    ref, bound = ar.ld_ref(y, gamma, lam, w, held, locs)
+    assert ref["num"].shape == (J, w + 1) and ref["cnt"].dtype == np.uint32 and ref["cnt"].tolist() == ldcnt
+    assert ar.ratio(np.array(ldnum, dtype=LD), ref["num"], bound["num"]) <= tiny
+    assert ar.ratio(np.array(ldabs, dtype=LD), ref["absn"], bound["num"]) <= tiny
+    assert ldcnt[2][1] == ldcnt[2][0] == ldcnt[3][0] and ldcnt[3][2] == 0 and ref["num"][4, 1] == 0  # the repeat; past the end
+    wide = ar.ld_ref(y, gamma, lam, 7, held, locs)[0]  # (wider than the list: the band from the full product)
+    assert np.array_equal(wide["cnt"][:, :w + 1], ref["cnt"]) and np.all(wide["cnt"][:, J:] == 0) and np.all(wide["num"][:, J:] == 0)
+    assert ar.ratio(wide["num"][:, :w + 1], ref["num"], bound["num"]) <= tiny
+    narrow, nbound = ar.ld_ref(y, gamma, lam, 1, held, locs)  # (a narrow band: the shifted products)
+    assert np.array_equal(narrow["cnt"], ref["cnt"][:, :2]) and ar.ratio(narrow["num"], ref["num"][:, :2], bound["num"][:, :2]) <= tiny
+    assert ar.ratio(nbound["num"], bound["num"][:, :2], bound["num"][:, :2]) <= tiny
     # fold-in, two updates
     g = [[LD(gamma[i, a]) for a in range(k)] for i in range(n)]
     for it in (1, 2):
@@ -204,6 +253,11 @@ def test_the_references_equal_a_brute_force_loop():
 def test_fp64_numpy_lies_within_half_of_every_bound_every_k(k):
     c = ar.plant_every_k(k)
     print(k, compare_all(Fp64(c), c, all_refs(c)))
+    c = ar.plant_every_k(k, n=602, l=150)  # the GPU test's shape of tsamd_ld
+    print(k, "ld", compare_ld_lists(Fp64(c), c, ld_refs(c, 65), 65))
+
+
+LATE_LD_WINDOW = 39  # l - 1 of the widest late shape: every pair of either list
 
 
 @pytest.fixture(scope="module")
@@ -213,6 +267,8 @@ def late_refs():
     for shape in ar.LATE_SHAPES:
         c, _ = ar.plant_late(*shape)
         out[shape] = (c, all_refs(c, c.shard, iters=(1, 5)))
+        out[shape][1]["ld_lists"] = ld_refs(c, LATE_LD_WINDOW, c.shard)
+        out[shape][1]["ld"] = out[shape][1]["ld_lists"]["list"]
     return out
 
 
@@ -221,6 +277,9 @@ def test_fp64_numpy_lies_within_half_of_every_bound_late_state(late_refs, shape)
     c, refs = late_refs[shape]
     e = ar.Entries(c.y, c.gamma, c.lam, c.held, None, c.shard)
     print(shape, "min q %.2e min 1-q %.2e" % (float(e.q.min()), float(e.omq.min())), compare_all(Fp64(c, c.shard), c, refs, c.shard, iters=(1, 5)))
+    z = np.where(e.ok, e.r / np.sqrt(e.h), 0)
+    print(shape, "max |z| %.0f" % float(np.abs(z).max()), "ld", compare_ld_lists(Fp64(c, c.shard), c, refs["ld_lists"], LATE_LD_WINDOW),
+          "worst bound / sum |z z| %.2e" % float(np.max(refs["ld_lists"]["all"][1]["num"] / np.maximum(refs["ld_lists"]["all"][0]["absn"], LD("1e-300")))))
     eb = ar.ebeta_ref(c.lam)
     assert eb.min() < 1e-4 and 1 - eb.max() < 1e-4 and c.gamma.min() == 1e-8 and c.gamma.max() > 1e5  # late indeed
     # a floor row's w underflows: one update puts its floor components at alpha exactly
@@ -239,7 +298,8 @@ def outside(f, c, refs, shard, families):
     tr = c.trait[shard[0]:shard[0] + shard[1]]
     calls = dict(loglik=lambda: ar.compare_loglik(f.loglik(c.locs), *refs["loglik"]), scan=lambda: ar.compare_scan(f.scan(c.locs, tr), *refs["scan"]),
                  kin=lambda: ar.compare_kin(f.kin(c.ids, c.locs), *refs["kin"]),
-                 foldin=lambda: ar.compare_foldin(*f.foldin(c.locs, 1), refs["foldin"][1]))
+                 foldin=lambda: ar.compare_foldin(*f.foldin(c.locs, 1), refs["foldin"][1]),
+                 ld=lambda: ar.compare_ld(f.ld(c.locs, LATE_LD_WINDOW), *refs["ld"]))
     out = set()
     for name in families:
         try:
@@ -252,7 +312,7 @@ def outside(f, c, refs, shard, families):
 def test_each_mutation_leaves_a_bound(late_refs):
     shape = ar.LATE_SHAPES[0]
     c, refs = late_refs[shape]
-    shard, every = c.shard, {"loglik", "scan", "kin", "foldin"}
+    shard, every = c.shard, {"loglik", "scan", "kin", "foldin", "ld"}
     assert outside(Fp64(c, shard), c, refs, shard, every) == set()
     ll, llb = refs["loglik"]
     e = ar.Entries(c.y, c.gamma, c.lam, c.held, c.locs, shard)
@@ -272,6 +332,27 @@ def test_each_mutation_leaves_a_bound(late_refs):
     f = Fp64(c, shard)
     f.theta[n0, k0] *= 1.0 + 1e-9
     assert outside(f, c, refs, shard, {"loglik", "scan", "kin"}) == {"loglik", "scan", "kin"}
+    # tsamd_ld sums over every individual of the shard: the largest GAMMA component of individual 17 scaled by 1 + 1e-9 and
+    # the row normalised again, a far smaller step (theta_k moves by 1e-9 theta_k (1 - theta_k), q by 1e-9 theta_k
+    # (Ebeta_k - q)).  With dz/dq = -2 / sqrt(h) - z (1 - 2q) / h the exact change of the individual's own term of a pair,
+    # z_i dz_j + z_j dz_i, is more than 1.5 times the bound in one entry of the band
+    n0 = 17
+    k0 = int(np.argmax(c.gamma[n0]))
+    q, h = e.q[:, n0], e.h[:, n0]
+    dq = LD(1e-9) * ar.theta_ref(c.gamma[n0:n0 + 1])[0, k0] * (ar.ebeta_ref(c.lam[e.locs])[:, k0] - q)
+    z = e.r[:, n0] / np.sqrt(h)
+    z = np.where(e.ok[:, n0], z, 0)
+    dz = np.where(e.ok[:, n0], (-2 / np.sqrt(h) - z * (1 - 2 * q) / h) * dq, 0)
+    change = np.abs(ar._band(np.outer(z, dz) + np.outer(dz, z), LATE_LD_WINDOW))
+    bound = refs["ld"][1]["num"]
+    over = float(np.max(np.where(change > 0, change / np.where(bound > 0, bound, 1), 0)))
+    print("ld, gamma[17][%d] scaled by 1 + 1e-9: exact change / bound = %.2f" % (k0, over))
+    assert over >= 1.5  # (section 2: the fp64 evaluation's own error takes at most 0.5 of the bound back)
+    f = Fp64(c, shard)
+    g = f.gamma[n0].copy()
+    g[k0] *= 1.0 + 1e-9
+    f.theta[n0] = g / g.sum()
+    assert outside(f, c, refs, shard, {"ld"}) == {"ld"}
 
     # two neighbouring individuals' genotypes swapped at one listed location: both listed ids' neighbours would do; take the
     # first listed location and the first pair (n, n + 1) with n listed, both stored and phenotyped, different genotypes and
@@ -300,7 +381,10 @@ def test_each_mutation_leaves_a_bound(late_refs):
     f = Fp64(c, shard)
     assert f.ys[loc, n1] == 3 and c.y[loc, n1] != 3
     f.ys[loc, n1] = c.y[loc, n1]
-    assert outside(f, c, refs, shard, {"loglik", "scan", "foldin"}) == {"loglik", "scan", "foldin"}
+    assert outside(f, c, refs, shard, {"loglik", "scan", "foldin", "ld"}) == {"loglik", "scan", "foldin", "ld"}
+    got = f.ld(c.locs, LATE_LD_WINDOW)
+    row = list(c.locs).index(loc)
+    assert got["cnt"][row, 0] == refs["ld"][0]["cnt"][row, 0] + 1  # (the count it is: ratio() alone would not see it)
     ids = c.ids.copy()
     ids[1] = n1  # (the kinship list need not hold that individual: put it there)
     kin_refs = dict(kin=ar.kin_ref(c.y, c.gamma, c.lam, ids, c.held, c.locs, shard))
@@ -316,6 +400,27 @@ def test_each_mutation_leaves_a_bound(late_refs):
     f = Fp64(c, shard)
     f.lam[loc] = f.lam[loc][:, ::-1]
     assert outside(f, c, refs, shard, every) == every
+
+
+def test_a_band_read_one_column_off_leaves_the_bound(late_refs):
+    """tsamd_ld's own wrong read-out: column d + 1 of the band where d belongs (the last column 0), the counts as they are"""
+    c, refs = late_refs[ar.LATE_SHAPES[0]]
+    ref, bound = refs["ld"]
+    got = Fp64(c, c.shard).ld(c.locs, LATE_LD_WINDOW)
+    assert ar.compare_ld(got, ref, bound) <= 0.5
+    off = dict(num=np.concatenate([got["num"][:, 1:], np.zeros((len(c.locs), 1))], axis=1), cnt=got["cnt"])
+    with pytest.raises(AssertionError):
+        ar.compare_ld(off, ref, bound)
+    # and the counts one column off on their own
+    off = dict(num=got["num"], cnt=np.concatenate([got["cnt"][:, 1:], np.zeros((len(c.locs), 1), dtype=np.uint32)], axis=1))
+    with pytest.raises(AssertionError):
+        ar.compare_ld(off, ref, bound)
+
+
+def test_fp64_numpy_ld_lies_within_half_of_the_bound_at_the_wide_late_shape():
+    """(1030, 150, 8), window 65: the late shape the GPU test runs under the test hooks (three location tiles, two overlap tiles)"""
+    c, _ = ar.plant_late(1030, 150, 8)
+    print("late (1030, 150, 8) ld", compare_ld_lists(Fp64(c, c.shard), c, ld_refs(c, 65, c.shard), 65))
 
 
 # -- 4. plant() without n_eff is what it was -------------------------------------------------------------------------------------------

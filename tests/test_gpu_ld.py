@@ -1,7 +1,8 @@
 """tsamd_ld: structure-adjusted LD of nearby listed locations on the matrix cores, and the pruning built on it.
 
 The reference is numpy fp64 from reads of the engine only -- get_theta(), get_ebeta() and download_bed() (which shows held-out
-entries as missing, as wanted):
+entries as missing, as wanted; tests/test_gpu_ld_refs.py holds the call to a long-double reference from the planted inputs alone,
+within a derived bound, at every K and from a late-training state):
     q = theta[n] . Ebeta[j],  h = 2q (1 - q),  z = (y - 2q) / sqrt(h),  m = 1,  both 0 where the stored code is 01 or h <= 0
     num[i][d] = sum_n z(n, i) z(n, i + d),  cnt[i][d] = sum_n m(n, i) m(n, i + d),  0 where i + d is past the list
 
